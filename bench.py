@@ -17,10 +17,17 @@ N > 1 : BASELINE.json configs[3] (San-Miguel-class scene, 30 % alpha-tested + te
         --composer peer: stores into hipIpc-mapped images, no collective).  Without a launcher around it (no WORLD_SIZE) `--gpus N` starts its
         own N ranks; it never reports a 1-GPU number for an N-GPU request.  `--emulate-rank R` renders one rank's share alone on one GPU.
 
-Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (largest mean stage time):
-algorithmic bytes of SURVEY.md 8(d) / mean launch duration from HIP events on the execute stream.
-`cpu_baseline` times the CPU oracle (a port of the reference HLSL; test infrastructure) on one
+Prints ONE JSON line on rank 0.  A plain run measures the line's own value only: it sets up, warms up, times exactly --steps steps
+(one region, no HIP events inside it), writes --dump-outputs if asked and prints the line.  Everything else moves behind --full:
+  --full   the timed region repeated (5 regions when --steps < 200, the median reported), the per-stage profile and `roofline`, the
+           camera-path legs (`path`, `path_fast`), the CPU baselines, the other workloads measured beside the headline (`configs1`,
+           `configs3`, `dense`, `skinned`, `configs4`) and, for N > 1, every leg of the plan beside the line's own and the one-GPU frame
+           each leg is measured against (`n1_reference`, `efficiency_vs_n1`).
+`roofline` is for the dominant kernel (largest mean stage time): algorithmic bytes of SURVEY.md 8(d) / mean launch duration from HIP
+events on the execute stream.  `cpu_baseline` times the CPU oracle (a port of the reference HLSL; test infrastructure) on one
 frame of the same workload, rank 0, N = 1 only.
+--dump-outputs DIR (--gpus 1 only): after the timed region, what its last step computed (the pass's HDR target, linear depth and visibility buffer as
+a caller reads them back, at a fixed seeded sample of pixels, and its visible-cluster counters) as DIR/<name>.npy in float32 / float64.
 """
 import argparse
 import json
@@ -91,7 +98,12 @@ def main():
     ap.add_argument("--camera-path", type=int, default=200,
                     help="N = 1 only: after the static-camera region, K frames along the preset's camera path (a new camera every frame, so that phase 2 of the "
                          "occlusion chain has work) reported as `path`; 0 skips it")
-    ap.add_argument("--repeats", type=int, default=0, help="timed regions of --steps frames each; the median is reported.  0 = 5 when --steps < 200, else 1")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the line's own value (repeated regions, stage profile and roofline, camera paths, CPU baselines, the other "
+                         "workloads and legs); a plain run times --steps steps of the headline once")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, a fixed seeded sample of pixels; under 64 MB)")
+    ap.add_argument("--repeats", type=int, default=0, help="timed regions of --steps frames each; the median is reported.  0 = 1, or with --full 5 when --steps < 200, else 1")
     ap.add_argument("--occlusion", type=int, default=1, choices=[0, 1],
                     help="2-phase HZB occlusion culling (reference default: on, BR/include/Renderer.h:220); timed frames are steady state")
     ap.add_argument("--lod-builder", default=None, choices=["quadtree", "own"],
@@ -145,6 +157,10 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         fail_line(args, "--gpus must be >= 1")
+    if args.dump_outputs and (args.gpus > 1 or args.emulate_rank is not None):
+        # the N-GPU frame is composed across ranks, and the balanced partition's bands follow measured frame times: a rank's surfaces are not a
+        # reproducible output of the path
+        fail_line(args, "--dump-outputs is for --gpus 1 only")
     args.workload_given = args.workload is not None
     if args.workload is None:
         args.workload = "bistro" if args.gpus == 1 else "san_miguel"
@@ -195,28 +211,29 @@ def main():
         if out is not None and args.shared_gpu:
             out["shared_gpu"] = f"all {world} ranks rendered on ONE GPU (gloo + the peer-write composer between the processes): a check of the N-rank control flow, not an N-GPU measurement"
     else:
-        out = measure(args, args.workload, world, rank, local_rank, cpu=(world == 1 and not args.no_cpu_baseline))
-    if world == 1 and not args.no_second and args.workload != "sponza":
+        out = measure(args, args.workload, world, rank, local_rank, cpu=(args.full and world == 1 and not args.no_cpu_baseline), path=args.full, dump=args.dump_outputs)
+    extras = world == 1 and args.full
+    if extras and not args.no_second and args.workload != "sponza":
         # the metric string's own wording ("vis-buffer+resolve") is configs[1]: measured by the same run, reported beside the target frame
         second = measure(args, "sponza", world, rank, local_rank, cpu=False, path=False)
         if out is not None:
             out["configs1"] = {k: second[k] for k in ("value", "unit", "ms_per_step", "ms_per_step_minmax", "config", "roofline", "stage_ms") if k in second}
-    if world == 1 and not args.no_third and args.workload != "san_miguel":
+    if extras and not args.no_third and args.workload != "san_miguel":
         # configs[3]'s frame as SURVEY.md 8(d) config 4 states it -- 30 % alpha-tested, texture-sampled materials -- on one GPU, under the same clock
         third = measure(args, "san_miguel", world, rank, local_rank, cpu=False, path="path")       # (its camera-path leg too: phase 2 of the alpha-tested scene)
         if out is not None:
             out["configs3"] = {k: third[k] for k in ("value", "unit", "ms_per_step", "ms_per_step_minmax", "config", "roofline", "stage_ms", "serial_frame_ms", "path") if k in third}
-    if world == 1 and not args.no_dense and args.workload != "bistro_dense":
+    if extras and not args.no_dense and args.workload != "bistro_dense":
         # SURVEY.md 8 a-3 / a-5's regime (tens of thousands of visible clusters, pixel-sized triangles) under the same clock as the headline
         dense = measure(args, "bistro_dense", world, rank, local_rank, cpu=False, path=False)
         if out is not None:
             out["dense"] = {k: dense[k] for k in ("value", "unit", "ms_per_step", "ms_per_step_minmax", "config", "roofline", "stage_ms", "serial_frame_ms") if k in dense}
-    if world == 1 and not args.no_skinned and args.workload != "bistro_skinned":
+    if extras and not args.no_skinned and args.workload != "bistro_skinned":
         # row a-10 under the same clock: the headline frame with 30 % of its instances skinned
         sk = measure(args, "bistro_skinned", world, rank, local_rank, cpu=False, path=False)
         if out is not None:
             out["skinned"] = {k: sk[k] for k in ("value", "unit", "ms_per_step", "ms_per_step_minmax", "config", "stage_ms", "serial_frame_ms") if k in sk}
-    if world == 1 and not args.no_fourth and args.workload != "zorah":
+    if extras and not args.no_fourth and args.workload != "zorah":
         # configs[4]'s frame on one GPU: 8K, 100 k instances, ~670 k visible clusters -- the LOD-select regime (rows a-2 / a-3 / a-10) under the same clock
         fourth = measure(args, "zorah", world, rank, local_rank, cpu=False, path=False)
         if out is not None:
@@ -234,7 +251,8 @@ def main():
 
 
 def multi_gpu_legs(args, n, rank, local_rank, emulated):
-    """--gpus N > 1.  Legs under one clock, and the one-GPU frame each of them is measured against, made inside the same job (which scenes: `plan` below):
+    """--gpus N > 1.  Legs under one clock, and with --full the one-GPU frame each of them is measured against, made inside the same job (which scenes:
+    `plan` below; a plain run measures the plan's first leg alone, the line's own value):
       weak    every rank shades one 4K frame's worth of pixels: the frame is 7680 x 1088 N, interleaved partition in chunks of --stripe-rows rows; the
               reference is the scene's 3840 x 2160 frame on one GPU (rank 0's; every rank renders it, each on its own GPU)
       strong  THE 4K frame (3840 x 2176: 2160 rows padded to a multiple of 16 N) split N ways in chunks of 128 / N rows; the reference is that frame on one GPU
@@ -246,6 +264,8 @@ def multi_gpu_legs(args, n, rank, local_rank, emulated):
     # the driver's runs compares one scene with itself -- and configs[3]'s scene (San-Miguel-class, what BASELINE.json names for the partition) runs both legs beside it, under
     # `configs3_weak` / `configs3_strong`, each with its own one-GPU reference.  With --workload: that scene's legs, `weak` / `strong`, as before.
     plan = [(leg, leg, args.workload) for leg in legs] if args.workload_given else [("weak", "weak", "bistro")] + [("configs3_" + leg, leg, "san_miguel") for leg in legs]
+    if not args.full:
+        plan = plan[:1]      # the line's own leg, with the one-GPU frame its efficiency is stated against
     result = {}
     for key, leg, wl in plan:
         if leg == "weak":
@@ -257,12 +277,15 @@ def multi_gpu_legs(args, n, rank, local_rank, emulated):
             frame, rows = compose.strong_frame(n)
             ref_frame = frame
         got = measure(args, wl, n, rank, local_rank, cpu=False, path=False, emulated=emulated, frame=frame, stripe_rows=rows, partition=part)
-        ref = measure(args, wl, 1, 0, local_rank, cpu=False, path=False, emulated=True, frame=ref_frame, solo=True)      # every rank, on its own GPU; rank 0's is reported
+        ref = None
+        if args.full:
+            ref = measure(args, wl, 1, 0, local_rank, cpu=False, path=False, emulated=True, frame=ref_frame, solo=True)      # every rank, on its own GPU; rank 0's is reported
         if got is not None:
             keep = ("value", "unit", "ms_per_step", "ms_per_step_minmax", "rank_ms_per_step", "config", "stage_ms", "serial_frame_ms", "host_issue_ms_per_step")
             entry = {k: got[k] for k in keep if k in got}
-            entry["n1_reference"] = {"value": ref["value"], "ms_per_step": ref["ms_per_step"], "frame": list(ref_frame), "pixels": ref_frame[0] * ref_frame[1]}
-            entry["efficiency_vs_n1"] = round(got["value"] / n / ref["value"], 4)
+            if ref is not None:
+                entry["n1_reference"] = {"value": ref["value"], "ms_per_step": ref["ms_per_step"], "frame": list(ref_frame), "pixels": ref_frame[0] * ref_frame[1]}
+                entry["efficiency_vs_n1"] = round(got["value"] / n / ref["value"], 4)
             entry["leg"] = leg
             result[key] = (got, entry)
     if not result:
@@ -275,10 +298,11 @@ def multi_gpu_legs(args, n, rank, local_rank, emulated):
     return out
 
 
-def measure(args, workload, n, rank, local_rank, cpu, path=True, emulated=False, frame=None, stripe_rows=None, solo=False, partition=None):
+def measure(args, workload, n, rank, local_rank, cpu, path=True, emulated=False, frame=None, stripe_rows=None, solo=False, partition=None, dump=None):
     """K timed steps of one workload on this rank's GPU (all ranks call it together); rank 0 returns the result object.
     frame: (W, H) instead of the workload's default; stripe_rows: chunk height of the interleaved partition instead of --stripe-rows; solo: a one-GPU
-    measurement inside an N-GPU job (no process group is touched; every rank returns its own result)."""
+    measurement inside an N-GPU job (no process group is touched; every rank returns its own result); dump: directory for the outputs of the
+    last timed step (rank 0).  Without --full only the timed region runs: no stage profile, no serial frames, no roofline."""
     import torch
     import torch.distributed as dist
     from basicrenderer_amd import Scene, compose
@@ -486,16 +510,20 @@ def measure(args, workload, n, rank, local_rank, cpu, path=True, emulated=False,
     if composer:
         composer.finish()
     torch.cuda.synchronize()
-    r.stage_times()                       # drop the warm-up window (first-frame effects)
-    serial_frames(10)                     # untimed: per-stage profile of the steady state, all stages
-    warm_ms = r.stage_times()
-    dom_stage = dominant_stage(workload, features, warm_ms)
-    longest_stage = max(warm_ms, key=lambda k: warm_ms[k]) if warm_ms else dom_stage      # this run's stage timers (whole stages: the raster stage is three kernels, two phases)
-    r.set_timed_stages([dom_stage])
-    # The timed region: EXACTLY --steps frames between a barrier + synchronize on both sides, MAX over ranks.  A short region (the driver's
-    # 20 steps are 9 ms) is one noisy sample, so it is repeated (--repeats; 5 when --steps < 200) and the MEDIAN region is reported, the
-    # spread beside it (`ms_per_step_minmax`); `steps` stays the per-region count.
-    repeats = args.repeats if args.repeats > 0 else (5 if args.steps < 200 else 1)
+    full = args.full
+    if full:
+        r.stage_times()                       # drop the warm-up window (first-frame effects)
+        serial_frames(10)                     # untimed: per-stage profile of the steady state, all stages
+        warm_ms = r.stage_times()
+        dom_stage = dominant_stage(workload, features, warm_ms)
+        longest_stage = max(warm_ms, key=lambda k: warm_ms[k]) if warm_ms else dom_stage      # this run's stage timers (whole stages: the raster stage is three kernels, two phases)
+        r.set_timed_stages([dom_stage])
+    else:
+        r.set_timed_stages([])                # a plain run: no HIP events inside the timed region
+    # The timed region: EXACTLY --steps frames between a barrier + synchronize on both sides, MAX over ranks.  With --full a short region
+    # (the driver's 20 steps are 9 ms) is one noisy sample, so it is repeated (--repeats; 5 when --steps < 200) and the MEDIAN region is
+    # reported, the spread beside it (`ms_per_step_minmax`); `steps` stays the per-region count.
+    repeats = args.repeats if args.repeats > 0 else (5 if full and args.steps < 200 else 1)
     regions, issue_s, own = [], [], []
     for _ in range(repeats):
         frame_no[0] = 0
@@ -533,17 +561,20 @@ def measure(args, workload, n, rank, local_rank, cpu, path=True, emulated=False,
             composer.wait_status()
         except Exception as e:      # noqa: BLE001
             fail_line(args, f"peer-write composer: {e}")
-    stage_ms = r.stage_times()          # mean over the last timed steps (HIP events on the execute stream); dominant stage only
-    in_flight_ms = None
-    if fif >= 2:
-        # the dominant kernel shared the CUs with the other pass's frame during the timed region: its own duration comes from serial frames
-        in_flight_ms = stage_ms[dom_stage]
-        serial_ms = serial_frames(min(args.steps, 200))
-        stage_ms = r.stage_times()
-    if warm_ms:
-        stage_ms = {k: (stage_ms[k] if k == dom_stage else warm_ms[k]) for k in warm_ms}
-    per_stage_bytes, total_bytes = r.algorithmic_bytes()
-    launched_bytes, _ = r.algorithmic_bytes_launched()
+    if dump and (rank == 0 or emulated or solo):
+        dump_outputs(dump, passes[(args.steps - 1) % len(passes)])      # the pass that rendered the last timed step, before anything renders again
+    if full:
+        stage_ms = r.stage_times()          # mean over the last timed steps (HIP events on the execute stream); dominant stage only
+        in_flight_ms = None
+        if fif >= 2:
+            # the dominant kernel shared the CUs with the other pass's frame during the timed region: its own duration comes from serial frames
+            in_flight_ms = stage_ms[dom_stage]
+            serial_ms = serial_frames(min(args.steps, 200))
+            stage_ms = r.stage_times()
+        if warm_ms:
+            stage_ms = {k: (stage_ms[k] if k == dom_stage else warm_ms[k]) for k in warm_ms}
+        per_stage_bytes, total_bytes = r.algorithmic_bytes()
+        launched_bytes, _ = r.algorithmic_bytes_launched()
     c = r.counters()
     path_out, path_fast_out = None, None
     if path and n == 1 and args.camera_path > 0 and args.occlusion:
@@ -555,52 +586,53 @@ def measure(args, workload, n, rank, local_rank, cpu, path=True, emulated=False,
         shaded = W * H if balanced else W * (band[1] - band[0]) * n            # pixels dispatched per step, all ranks
         ms_per_step = dt / args.steps * 1e3
         value = shaded / 1e6 / (dt / args.steps)
-        dom = dom_stage if stage_ms.get(dom_stage, 0.0) > 0 else max(stage_ms, key=lambda k: stage_ms[k])      # the stage the events stayed around (two stages within noise of each other must not swap here)
-        dom_s = stage_ms[dom] * 1e-3
-        achieved = per_stage_bytes[dom] / dom_s / 1e9 if dom_s > 0 else 0.0
-        frame_gbs = total_bytes / (dt / args.steps) / 1e9
-        # From the committed rocprofv3 passes of this same command (tools/profile.sh): HBM-side bytes of the dominant kernel per launch
-        # (FETCH_SIZE x 2 on gfx950 + WRITE_SIZE) and its VALU instruction count (SQ_INSTS_VALU).  null when no profile of this
-        # workload / kernel is committed.
-        traffic, valu = None, None
-        try:
-            tag = PROFILE_TAG.get((workload, features), "none")
-            if not os.path.exists(os.path.join(ROOT, "profiles", tag + "_traffic.json")):
-                tag = PROFILE_FALLBACK.get(tag, tag)
-            tj = json.load(open(os.path.join(ROOT, "profiles", tag + "_traffic.json")))
-            # the stage's kernels; template instantiations ("k_shade<0>", "k_raster<true>") are matched by base name.  A one-kernel stage reports
-            # the instantiation that takes the most time per launch; the raster stage is three kernels launched once per occlusion phase, and
-            # its traffic is their sum over the frame's launches (the committed averages are per launch, over both phases' launches)
-            stage_kernels = {"raster": ["k_raster", "k_raster_emit", "k_raster_wide", "k_raster_bins", "k_raster_overflow"]}.get(dom, [DOMINANT_KERNEL.get(dom, dom).split("<")[0]])
-            traffic_sum, wi, found = 0, 0, False
-            for base in stage_kernels:
-                # (instantiations the steady state launches: a variant the first frames of a run took -- the in-place G-buffer kernel while the pass had no depth chain to cull against --
-                # has a handful of calls in the trace and is not this frame's kernel)
-                cands = [k for k in tj if k.split("<")[0] == base and tj[k].get("calls_per_frame", 1.0) >= 0.5]
-                if n == 1 and cands:
-                    rec = tj[max(cands, key=lambda k: tj[k].get("avg_us", 0.0))]
-                    # launches per frame of THIS kernel in the committed --kernel-trace --stats run (Calls / frames; tools/pmc_report.py): since phase 2
-                    # rasterises directly while it is small, k_raster runs twice per frame but k_raster_bins / k_raster_overflow once
-                    per_frame = rec.get("calls_per_frame") or (2 if (dom == "raster" and args.occlusion) else 1)
-                    traffic_sum += rec["hbm_bytes_per_launch"] * per_frame
-                    wi += rec.get("valu_wave_insts_per_launch", 0) * per_frame
-                    found = True
-            if found:
-                traffic = int(traffic_sum)
-                if wi:
-                    # the microarchitecture guide's issue peak: one wave64 VALU instruction per 2 cycles per SIMD, 1024 SIMDs, 2.4 GHz
-                    valu = {"wave_insts": int(wi), "insts_per_px": round(wi * 64.0 / (W * (band[1] - band[0])), 1), "peak_wave_insts_per_s": VALU_PEAK_WAVE_INSTS,
-                            "frac": round(wi / dom_s / VALU_PEAK_WAVE_INSTS, 5), "peak_measured_wave_insts_per_s": VALU_PEAK_MEASURED,
-                            "frac_of_measured_peak": round(wi / dom_s / VALU_PEAK_MEASURED, 5),
-                            "source": "SQ_INSTS_VALU of the committed profile / this run's launch time; measured peak: tools/valu_issue_probe.hip (full-rate instructions)"}
-        except (OSError, ValueError, KeyError):
-            pass
-        hbm_frac = achieved / HBM_PEAK_GBS
-        # what the counters say the kernel MOVED (committed profile) over this run's launch time, and the bytes the launched variant is obliged to move (44 B / px of
-        # k_shade<0> when no material has a coat or fuzz layer, against 8(d)'s 60): `frac` keeps 8(d)'s definition, these two are the honest utilisation beside it
-        frac_traffic = round(traffic / dom_s / 1e9 / HBM_PEAK_GBS, 5) if (traffic and dom_s > 0) else None
-        frac_launched = round(launched_bytes[dom] / dom_s / 1e9 / HBM_PEAK_GBS, 5) if dom_s > 0 else None
-        nearer = "valu" if (valu and valu["frac"] > max(hbm_frac, frac_traffic or 0.0)) else "hbm"
+        if full:
+            dom = dom_stage if stage_ms.get(dom_stage, 0.0) > 0 else max(stage_ms, key=lambda k: stage_ms[k])      # the stage the events stayed around (two stages within noise of each other must not swap here)
+            dom_s = stage_ms[dom] * 1e-3
+            achieved = per_stage_bytes[dom] / dom_s / 1e9 if dom_s > 0 else 0.0
+            frame_gbs = total_bytes / (dt / args.steps) / 1e9
+            # From the committed rocprofv3 passes of this same command (tools/profile.sh): HBM-side bytes of the dominant kernel per launch
+            # (FETCH_SIZE x 2 on gfx950 + WRITE_SIZE) and its VALU instruction count (SQ_INSTS_VALU).  null when no profile of this
+            # workload / kernel is committed.
+            traffic, valu = None, None
+            try:
+                tag = PROFILE_TAG.get((workload, features), "none")
+                if not os.path.exists(os.path.join(ROOT, "profiles", tag + "_traffic.json")):
+                    tag = PROFILE_FALLBACK.get(tag, tag)
+                tj = json.load(open(os.path.join(ROOT, "profiles", tag + "_traffic.json")))
+                # the stage's kernels; template instantiations ("k_shade<0>", "k_raster<true>") are matched by base name.  A one-kernel stage reports
+                # the instantiation that takes the most time per launch; the raster stage is three kernels launched once per occlusion phase, and
+                # its traffic is their sum over the frame's launches (the committed averages are per launch, over both phases' launches)
+                stage_kernels = {"raster": ["k_raster", "k_raster_emit", "k_raster_wide", "k_raster_bins", "k_raster_overflow"]}.get(dom, [DOMINANT_KERNEL.get(dom, dom).split("<")[0]])
+                traffic_sum, wi, found = 0, 0, False
+                for base in stage_kernels:
+                    # (instantiations the steady state launches: a variant the first frames of a run took -- the in-place G-buffer kernel while the pass had no depth chain to cull against --
+                    # has a handful of calls in the trace and is not this frame's kernel)
+                    cands = [k for k in tj if k.split("<")[0] == base and tj[k].get("calls_per_frame", 1.0) >= 0.5]
+                    if n == 1 and cands:
+                        rec = tj[max(cands, key=lambda k: tj[k].get("avg_us", 0.0))]
+                        # launches per frame of THIS kernel in the committed --kernel-trace --stats run (Calls / frames; tools/pmc_report.py): since phase 2
+                        # rasterises directly while it is small, k_raster runs twice per frame but k_raster_bins / k_raster_overflow once
+                        per_frame = rec.get("calls_per_frame") or (2 if (dom == "raster" and args.occlusion) else 1)
+                        traffic_sum += rec["hbm_bytes_per_launch"] * per_frame
+                        wi += rec.get("valu_wave_insts_per_launch", 0) * per_frame
+                        found = True
+                if found:
+                    traffic = int(traffic_sum)
+                    if wi:
+                        # the microarchitecture guide's issue peak: one wave64 VALU instruction per 2 cycles per SIMD, 1024 SIMDs, 2.4 GHz
+                        valu = {"wave_insts": int(wi), "insts_per_px": round(wi * 64.0 / (W * (band[1] - band[0])), 1), "peak_wave_insts_per_s": VALU_PEAK_WAVE_INSTS,
+                                "frac": round(wi / dom_s / VALU_PEAK_WAVE_INSTS, 5), "peak_measured_wave_insts_per_s": VALU_PEAK_MEASURED,
+                                "frac_of_measured_peak": round(wi / dom_s / VALU_PEAK_MEASURED, 5),
+                                "source": "SQ_INSTS_VALU of the committed profile / this run's launch time; measured peak: tools/valu_issue_probe.hip (full-rate instructions)"}
+            except (OSError, ValueError, KeyError):
+                pass
+            hbm_frac = achieved / HBM_PEAK_GBS
+            # what the counters say the kernel MOVED (committed profile) over this run's launch time, and the bytes the launched variant is obliged to move (44 B / px of
+            # k_shade<0> when no material has a coat or fuzz layer, against 8(d)'s 60): `frac` keeps 8(d)'s definition, these two are the honest utilisation beside it
+            frac_traffic = round(traffic / dom_s / 1e9 / HBM_PEAK_GBS, 5) if (traffic and dom_s > 0) else None
+            frac_launched = round(launched_bytes[dom] / dom_s / 1e9 / HBM_PEAK_GBS, 5) if dom_s > 0 else None
+            nearer = "valu" if (valu and valu["frac"] > max(hbm_frac, frac_traffic or 0.0)) else "hbm"
         out = {
             "metric": "shaded Mpixels/s @4K (vis-buffer+resolve)" if (W, H) not in FRAME_SIZE.values() else f"shaded Mpixels/s @{W}x{H} (vis-buffer+resolve)", "value": round(value, 2), "unit": "Mpixels/s",
             "n_gpus": n, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
@@ -620,26 +652,27 @@ def measure(args, workload, n, rank, local_rank, cpu, path=True, emulated=False,
                        "occlusion_culling": bool(args.occlusion), "visible_clusters_phase2_rank0": int(c.visibleClustersPhase2),
                        "meshlets_tested_rank0": int(c.meshletsTested), "partition": (f"interleaved chunks of {stripe_rows} rows x{n}" if striped else ((f"cost-balanced contiguous bands x{n}" + (" (left at the equal split: composer fallback)" if balance_frozen else "")) if balanced else f"row bands x{n}")) if n > 1 else "single GPU",
                        "frames_in_flight": fif},
-            "roofline": {"bound": nearer, "bound_note": "the ceiling the kernel sits nearer to: VALU issue (roofline.valu.frac, SQ_INSTS_VALU of the committed profile) or HBM (frac / frac_traffic); "
-                                                        "achieved / peak / unit / frac are the HBM figures of SURVEY.md 8(d) either way",
-                         "kernel_stage": dom, "longest_stage_this_run": longest_stage, "kernel_stage_is_longest_stage": bool(dom == longest_stage),
-                         "kernel": {"raster": "k_raster (+ k_raster_emit, k_raster_wide) + k_raster_bins (+ k_raster_overflow), both occlusion phases"}.get(dom, DOMINANT_KERNEL.get(dom, dom)), "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(hbm_frac, 5), "traffic": traffic, "frac_traffic": frac_traffic, "valu": valu,
-                         "algorithmic_bytes_per_launch": int(per_stage_bytes[dom]), "algorithmic_bytes_launched_variant": int(launched_bytes[dom]), "frac_launched_variant": frac_launched,
-                         "launch_ms": round(stage_ms[dom], 4),
-                         "whole_frame": {"algorithmic_bytes": int(total_bytes), "achieved_GBps": round(frame_gbs, 2), "frac": round(frame_gbs / HBM_PEAK_GBS, 5)}},
-            "stage_ms": {k: round(v, 4) for k, v in stage_ms.items() if v > 0},
-            "stage_ms_note": (f"'{dom}' from HIP events inside the timed region; the other stages from 10 untimed frames before it" if fif == 1 else
-                              f"serial frames of one pass (nothing else on the GPU): '{dom}' over {min(args.steps, 200)} frames after the timed region, the other stages over 10 frames "
-                              f"before it; inside the timed region, sharing the CUs with the other pass's frame, '{dom}' took {in_flight_ms:.4f} ms per launch"),
         }
+        if full:
+            out["roofline"] = {"bound": nearer, "bound_note": "the ceiling the kernel sits nearer to: VALU issue (roofline.valu.frac, SQ_INSTS_VALU of the committed profile) or HBM (frac / frac_traffic); "
+                                                              "achieved / peak / unit / frac are the HBM figures of SURVEY.md 8(d) either way",
+                               "kernel_stage": dom, "longest_stage_this_run": longest_stage, "kernel_stage_is_longest_stage": bool(dom == longest_stage),
+                               "kernel": {"raster": "k_raster (+ k_raster_emit, k_raster_wide) + k_raster_bins (+ k_raster_overflow), both occlusion phases"}.get(dom, DOMINANT_KERNEL.get(dom, dom)), "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(hbm_frac, 5), "traffic": traffic, "frac_traffic": frac_traffic, "valu": valu,
+                               "algorithmic_bytes_per_launch": int(per_stage_bytes[dom]), "algorithmic_bytes_launched_variant": int(launched_bytes[dom]), "frac_launched_variant": frac_launched,
+                               "launch_ms": round(stage_ms[dom], 4),
+                               "whole_frame": {"algorithmic_bytes": int(total_bytes), "achieved_GBps": round(frame_gbs, 2), "frac": round(frame_gbs / HBM_PEAK_GBS, 5)}}
+            out["stage_ms"] = {k: round(v, 4) for k, v in stage_ms.items() if v > 0}
+            out["stage_ms_note"] = (f"'{dom}' from HIP events inside the timed region; the other stages from 10 untimed frames before it" if fif == 1 else
+                                    f"serial frames of one pass (nothing else on the GPU): '{dom}' over {min(args.steps, 200)} frames after the timed region, the other stages over 10 frames "
+                                    f"before it; inside the timed region, sharing the CUs with the other pass's frame, '{dom}' took {in_flight_ms:.4f} ms per launch")
         if balance_log is not None:
             out["balance_rounds"] = balance_log
             out["bounds"] = list(balancer.bounds)
         if n > 1:
             out["rank_ms_per_step"] = {"max": round(max(rank_ms), 4), "min": round(min(rank_ms), 4), "ranks": len(rank_ms),
                                        "note": "each rank's own time to finish the region's frames, composition included (emulated: this rank alone)"}
-        if fif >= 2:
+        if full and fif >= 2:
             out["roofline"]["launch_ms_in_flight"] = round(in_flight_ms, 4)
             out["serial_frame_ms"] = round(serial_ms, 4)      # one pass, one stream, frames back to back (what --frames-in-flight 1 times)
         if path_out is not None:
@@ -750,6 +783,29 @@ def camera_path(args, scene, passes, streams, shade_streams, r, dev, path_step):
             "replayed_records_mean": round(float(np.mean(replayed)), 1), "frames_in_flight": fif,
             "stage_ms": {k: round(v, 4) for k, v in stage_ms.items() if v > 0},
             "stage_ms_note": "serial frames of one pass over the same path (last 32 frames); ms_per_step is the in-flight arrangement of the timed region"}
+
+
+DUMP_PIXELS = 1 << 20      # --dump-outputs: pixels in the sample (36 MB of arrays; a whole 4K HDR target in float32 alone is 133 MB)
+
+
+def dump_outputs(directory, p):
+    """--dump-outputs: what a caller of pass `p` reads back after the timed region's last step, at DUMP_PIXELS pixels drawn without replacement
+    from a fixed seed (the same pixels for the same frame size), in row-major order of the frame:
+      hdr.npy         float32 [S, 4]  the lit target's RGBA16F channels
+      depth.npy       float32 [S]     linear depth
+      visibility.npy  float64 [S, 2]  high and low 32-bit words of the 64-bit visibility key
+      counters.npy    float64 [3]     visible clusters of occlusion phase 1 and phase 2, meshlets tested"""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    px = np.sort(np.random.default_rng(0).choice(p.H * p.W, size=min(p.H * p.W, DUMP_PIXELS), replace=False))
+    vis = p.visibility().reshape(-1)[px]
+    c = p.counters()
+    arrays = {"hdr": p.hdr().reshape(-1)[px].view(np.float16).reshape(-1, 4).astype(np.float32),
+              "depth": p.depth().reshape(-1)[px].astype(np.float32),
+              "visibility": np.stack([vis >> np.uint64(32), vis & np.uint64(0xFFFFFFFF)], 1).astype(np.float64),
+              "counters": np.array([c.visibleClusters, c.visibleClustersPhase2, c.meshletsTested], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def fail_line(args, why):

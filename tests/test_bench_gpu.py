@@ -24,7 +24,7 @@ def test_bench_runs_its_two_rank_flow_on_one_gpu():
         with socket.socket() as sock:
             sock.bind(("127.0.0.1", 0)); port = sock.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-               os.path.join(ROOT, "bench.py"), "--gpus", "2", "--shared-gpu", "--steps", "4", "--warmup", "3", "--balance-rounds", "2", "--balance-frames", "6"]
+               os.path.join(ROOT, "bench.py"), "--gpus", "2", "--shared-gpu", "--full", "--steps", "4", "--warmup", "3", "--balance-rounds", "2", "--balance-frames", "6"]
         done = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
         text = done.stdout.decode(errors="replace")
         if done.returncode == 0 or "a wait for a peer's band" not in text:
@@ -64,3 +64,38 @@ def test_bench_falls_back_to_peer_writes_when_rccl_refuses():
     out = json.loads([ln for ln in text.splitlines() if ln.startswith("{")][-1])
     assert out["n_gpus"] == 2 and out["value"] > 0
     assert "native composer failed" in out["config"]["workload"] and "peer" in out["config"]["workload"], out["config"]["workload"]
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_its_steps_once_and_dumps_the_same_outputs_twice(tmp_path):
+    """bench.py --gpus 1 as the driver runs it, twice with --dump-outputs: ONE line with the headline's fields, --steps frames timed in one region and nothing
+    of --full (no roofline, stage profile, camera paths, CPU baselines or other workloads); the last step's outputs as float32 / float64 .npy files under
+    64 MB, the same arrays in both runs."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", str(d)]
+        done = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+        text = done.stdout.decode(errors="replace")
+        assert done.returncode == 0, text[-4000:]
+        lines = [ln for ln in text.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, text[-4000:]
+        out = json.loads(lines[0])
+        assert out["n_gpus"] == 1 and out["steps"] == 3 and out["warmup"] == 2 and out["repeats"] == 1
+        assert out["metric"].startswith("shaded Mpixels/s") and out["unit"] == "Mpixels/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+        assert out["value"] > 0 and out["ms_per_step"] > 0 and out["ms_per_step_minmax"] == [out["ms_per_step"]] * 2
+        assert not {"roofline", "stage_ms", "serial_frame_ms", "path", "path_fast", "cpu_baseline", "configs0", "configs1", "configs3", "configs4", "dense", "skinned"} & set(out)
+        names = sorted(os.listdir(d))
+        assert names == ["counters.npy", "depth.npy", "hdr.npy", "visibility.npy"]
+        assert sum(os.path.getsize(d / n) for n in names) < 64 << 20
+        arrays = {n[: -len(".npy")]: np.load(d / n) for n in names}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert arrays["hdr"].shape == (1 << 20, 4) and arrays["depth"].shape == (1 << 20,) and arrays["visibility"].shape == (1 << 20, 2)
+        assert arrays["counters"][0] > 0 and (arrays["visibility"][:, 0] != 0xFFFFFFFF).any()      # something was drawn
+        dumps.append(arrays)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n], equal_nan=True), n

@@ -177,3 +177,19 @@ def test_interleaved_partition_is_a_partition_of_the_rows():
             raise AssertionError("accepted a chunk height that does not fit")
         except ValueError:
             pass
+
+
+def test_bench_refuses_dump_outputs_for_more_than_one_gpu(tmp_path):
+    """--dump-outputs is for --gpus 1: an N-GPU frame is composed across ranks and the balanced partition's bands follow measured frame times, so a
+    rank's surfaces are no reproducible output.  bench.py refuses before it starts a rank or touches a GPU: its error line, exit 2, nothing written."""
+    import json
+    import subprocess
+    for extra in (["--gpus", "2"], ["--gpus", "2", "--emulate-rank", "1"]):
+        d = tmp_path / "dump"
+        done = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)] + extra,
+                              cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
+        text = done.stdout.decode(errors="replace")
+        assert done.returncode == 2, text[-2000:]
+        out = json.loads([ln for ln in text.splitlines() if ln.startswith("{")][-1])
+        assert out["value"] is None and "--dump-outputs" in out["error"] and out["n_gpus"] == 2
+        assert not d.exists()

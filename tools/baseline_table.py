@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/baseline_table.py <bench line .json>  --  the GPU rows of BASELINE.md section 5 from one `python bench.py` line (value, frame time in flight and serial, algorithmic GB/s, fraction)."""
+"""tools/baseline_table.py <bench line .json>  --  the GPU rows of BASELINE.md section 5 from one `python bench.py --full` line (value, frame time in flight and serial, algorithmic GB/s, fraction)."""
 import json
 import sys
 

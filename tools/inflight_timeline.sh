@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: ktrace2.sh <workload> : two-stream timeline of steady-state frames (frames in flight = 2), from the timed region's middle
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rm -rf /tmp/kt; rocprofv3 --kernel-trace -d /tmp/kt -o a --output-format csv -- python3 bench.py --workload $1 --no-cpu-baseline --no-second --steps 40 --warmup 5 > /dev/null 2>&1
+rm -rf /tmp/kt; rocprofv3 --kernel-trace -d /tmp/kt -o a --output-format csv -- python3 bench.py --full --workload $1 --no-cpu-baseline --no-second --steps 40 --warmup 5 > /dev/null 2>&1
 python3 - <<PY
 import csv, glob
 f = glob.glob('/tmp/kt/**/a_kernel_trace.csv', recursive=True)[0]

@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=$1; shift
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/pt_$TAG; cd $ROOT; mkdir -p gpurun_out
-timeout 600 rocprofv3 --kernel-trace -d /tmp/pt_$TAG -o a --output-format csv -- python3 bench.py --no-cpu-baseline --no-second --no-third --no-dense --no-fourth --no-skinned --frames-in-flight 1 --steps 2 --warmup 1 --camera-path 120 "$@" > gpurun_out/path_timeline_$TAG.log 2>&1
+timeout 600 rocprofv3 --kernel-trace -d /tmp/pt_$TAG -o a --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-second --no-third --no-dense --no-fourth --no-skinned --frames-in-flight 1 --steps 2 --warmup 1 --camera-path 120 "$@" > $TMPDIR/path_timeline_$TAG.log 2>&1
 python3 - /tmp/pt_$TAG > gpurun_out/path_timeline_$TAG.txt <<'PY'
 import csv, glob, sys, collections
 f = glob.glob(sys.argv[1] + '/**/a_kernel_trace.csv', recursive=True)[0]
