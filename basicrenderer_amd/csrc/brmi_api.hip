@@ -132,7 +132,6 @@ static void compute_sizes(brmi_pass* p) {
     w.binPlan = take((uint64_t)(16 + 3 * p->binsX * p->binsY) * 4);
     w.binItems = take((uint64_t)p->binItemCapacity * 4);
     w.binScratch = take((uint64_t)std::max(1u, p->binScratchTiles) * 4096 * 8);
-    w.debugStamps = take(4096 + 1024 * 1024);      // instrumented builds (-DBRMI_TILE_STAMPS, possibly of one translation unit only) park per-phase cycle sums here
     w.clusterSetup = take((uint64_t)c.maxVisibleClusters * sizeof(ClusterSetup));
     // resolve arena: full tables (72 B per vertex + triangle slot) for up to 2^20 clusters = 9.7 GB of the 288; a configuration
     // that allows more visible clusters keeps the per-pixel path for the clusters that do not fit
@@ -243,13 +242,6 @@ static bool tuning_lookup(const char* key, long* out) {
     return false;
 }
 long tuning(const char* key, long def) { long v; return tuning_lookup(key, &v) ? v : def; }
-long experiment(const char* key, long def) {
-#ifdef BRMI_EXPERIMENTS
-    long v; return tuning_lookup(key, &v) ? v : def;
-#else
-    (void)key; return def;
-#endif
-}
 }  // namespace brmi
 extern "C" {
 
@@ -292,16 +284,6 @@ int brmi_create(const brmi_config* cfg, brmi_pass** out) {
     p->binOverflowPerStripe = (uint32_t)std::max(0l, tuning("bin_overflow", p->binOverflowPerStripe));
     p->binCapacity = (uint32_t)std::min(65536l, std::max(1l, tuning("bin_capacity", p->binCapacity)));   // 16-bit record indices inside a bin slice's alpha list; 65536 x 64 B x bins is far beyond any frame
     if (const long v = tuning("big_tri_area", 0)) p->bigTriArea = p->bigTriAreaAlpha = p->bigTriAreaDense = (int)std::max(1l, v);
-    // A/B switches of the experiment logs: only in builds with -DBRMI_EXPERIMENTS
-    p->rasterGrid = (uint32_t)std::max(64l, experiment("raster_grid", p->rasterGrid));
-    p->shadeGridShared = (uint32_t)std::min(65535l, std::max(256l, experiment("shade_grid_shared", p->shadeGridShared)));
-    p->gbufferGridShared = (uint32_t)std::min(65535l, std::max(256l, experiment("gbuffer_grid_shared", p->gbufferGridShared)));
-    p->clearRiderBlocks = (uint32_t)std::min(65535l, std::max(64l, experiment("clear_rider_blocks", p->clearRiderBlocks)));
-    p->wideFlat = experiment("flat_wide", 1) != 0;
-    p->scanChained = experiment("scan_chained", 1) != 0;
-    p->spillWidth = (uint32_t)std::min(1024l, std::max(128l, experiment("spill_width", p->spillWidth)));
-    p->rasterDebug = (int)experiment("raster_debug", 0);
-    if (const long v = experiment("big_tri_area_alpha", 0)) p->bigTriAreaAlpha = (int)std::max(1l, v);
     compute_sizes(p);
     *out = p;
     return BRMI_OK;
@@ -723,13 +705,10 @@ int brmi_update(brmi_pass* p, const brmi_frame_update* u, brmi_stream stream) {
 
 // What a frame's first launch has to wait for when frames are in flight (brmi_execute_split, and the stage entry points that start a frame:
 // a graph that schedules the stages itself after a split frame gets the same ordering).  No-ops when nothing was recorded.
-// flags of the events that order the two halves of split frames (experiments: BRMI_EVENT_FLAGS, e.g. 0x2 | 0x40000000 = no timing, device-scope release)
-static unsigned sync_event_flags() { static const unsigned f = (unsigned)experiment("event_flags", (long)hipEventDisableTiming); return f; }
-static int dbg_events() { static const int m = (int)experiment("debug_events", 0); return m; }      // (builds with -DBRMI_EXPERIMENTS only: events NOT issued)
 static int wait_for_frames_in_flight(brmi_pass* p, brmi_stream stream) {
     if (p->frameWaitsIssued) return BRMI_OK;      // brmi_execute_split has issued them for this frame: the stage entry points it calls do not repeat them
     // this pass's previous frame may still be resolving / shading on the other stream: its visibility buffer and tables are about to be rewritten
-    if (p->frameDoneRecorded && !(dbg_events() & 16)) BRMI_HIP(p, hipStreamWaitEvent(static_cast<hipStream_t>(stream), p->frameDone, 0));
+    if (p->frameDoneRecorded) BRMI_HIP(p, hipStreamWaitEvent(static_cast<hipStream_t>(stream), p->frameDone, 0));
     p->frameDoneRecorded = false;
     // frames in flight: this frame's phase 1 reads the chain the source pass built for the frame before, possibly on another stream
     // (recorded on this very stream -- the passes of a ring share their geometry stream --: stream order already says so, and every wait
@@ -835,18 +814,11 @@ int brmi_execute_split(brmi_pass* p, brmi_stream stream, brmi_stream shadeStream
     p->frameWaitsIssued = true;
     // When the phase-1 traversal is the one-launch LDS walk and the frame constants are due anyway, the frame needs no clear launch: the
     // constants kernel zeroes the culling state and the walk's launch carries the visibility clear (brmi_cull.hip, SideClear).
-    static const bool rideEnv = experiment("clear_rides", 1) != 0;
-    const bool rides = rideEnv && p->constantsSerial != p->updateSerial && p->minLevelWidth <= 1024u /* the one-launch walk runs (brmi_cull.hip: HIER_CAP_MAX) */ && !p->forceLevelKernels && p->scene.activeDrawCount != 0u;
+    const bool rides = p->constantsSerial != p->updateSerial && p->minLevelWidth <= 1024u /* the one-launch walk runs (brmi_cull.hip: HIER_CAP_MAX) */ && !p->forceLevelKernels && p->scene.activeDrawCount != 0u;
     p->lightGridDone = false;
     // A split frame (round 4): the riders move to where they fit -- the visibility clear onto k_cull_clusters' launch (brmi_cull.hip: ClearRide), the
     // light clustering onto the shading stream, which is idle until this frame's pixel pass (below, behind the same event as the early resolve setup).
-    static const bool sideEnv = experiment("side_riders", 1) != 0;
-    // where the per-cluster resolve tables of a split frame are made (BRMI_EARLY_RESOLVE_SETUP): 0 = at the end of the geometry stream, 1 = for the phase-1
-    // clusters on the shading stream beside the rasteriser (an event after the culling), 2 = on the shading stream in front of the pixel pass (no event)
-    static const int setupWhere = (int)experiment("early_resolve_setup", 1);
-    const bool earlySetup = split && setupWhere == 1;      // (a frame that resolves without tables launches nothing there: launch_resolve_setup)
-    const bool lateSetup = split && setupWhere == 2;
-    const bool sideRiders = rides && split && sideEnv && (p->bandPixelCount & 1ull) == 0ull;
+    const bool sideRiders = rides && split && (p->bandPixelCount & 1ull) == 0ull;
     if (sideRiders) {
         p->clearFrameStateWithConstants = true; p->clearVisibilityWithClusterCull = true;
         rc = brmi_cull(p, 1, stream);
@@ -868,13 +840,12 @@ int brmi_execute_split(brmi_pass* p, brmi_stream stream, brmi_stream shadeStream
     }
     // The per-cluster resolve tables need the cluster list, not the keys: for the phase-1 clusters they are made NOW, on the shading stream (idle until
     // this frame's pixel pass), beside the rasteriser -- the geometry half is a chain of latency-bound launches and this one was 40 us at its end.
-    // (Not on frames of more triangles than pixels, whose setup skips clusters that own no pixel and so needs the final keys.)
-    if (earlySetup) {
-        if (!p->cullDone) BRMI_HIP(p, hipEventCreateWithFlags(&p->cullDone, sync_event_flags()));
-        if (!(dbg_events() & 1)) {
+    // (Not on frames of more triangles than pixels, whose setup skips clusters that own no pixel and so needs the final keys; a frame that resolves
+    // without tables launches nothing there: launch_resolve_setup.)
+    if (split) {
+        if (!p->cullDone) BRMI_HIP(p, hipEventCreateWithFlags(&p->cullDone, hipEventDisableTiming));
         BRMI_HIP(p, hipEventRecord(p->cullDone, static_cast<hipStream_t>(stream)));
         BRMI_HIP(p, hipStreamWaitEvent(static_cast<hipStream_t>(shadeStream), p->cullDone, 0));
-        }
         if (sideRiders) { if ((rc = brmi::launch_light_clustering(p, static_cast<hipStream_t>(shadeStream)))) return rc; p->lightGridDone = true; }
         if ((rc = launch_resolve_setup(p, static_cast<hipStream_t>(shadeStream), 1u))) return rc;
     }
@@ -893,38 +864,33 @@ int brmi_execute_split(brmi_pass* p, brmi_stream stream, brmi_stream shadeStream
         // renders the next frame on another stream (brmi_set_history_source) can start while this frame is resolved and shaded.
         if ((rc = build_hzb_fused(p, static_cast<hipStream_t>(stream), true, true))) return rc;
         // recorded every frame (a pass may be linked to this one later, from another stream)
-        if (!p->chainReady) BRMI_HIP(p, hipEventCreateWithFlags(&p->chainReady, sync_event_flags()));
-        if (!(dbg_events() & 2)) { BRMI_HIP(p, hipEventRecord(p->chainReady, static_cast<hipStream_t>(stream))); p->chainRecorded = true; p->chainStream = stream; }
+        if (!p->chainReady) BRMI_HIP(p, hipEventCreateWithFlags(&p->chainReady, hipEventDisableTiming));
+        BRMI_HIP(p, hipEventRecord(p->chainReady, static_cast<hipStream_t>(stream)));
+        p->chainRecorded = true; p->chainStream = stream;
     }
     if (split) {
-        if (!lateSetup) {
-            if ((rc = launch_resolve_setup(p, static_cast<hipStream_t>(stream), earlySetup ? 2u : 0u))) return rc;
-            p->resolveSetupDone = true;
-        }
-        if (!p->geometryDone) BRMI_HIP(p, hipEventCreateWithFlags(&p->geometryDone, sync_event_flags()));
-        if (!p->frameDone) BRMI_HIP(p, hipEventCreateWithFlags(&p->frameDone, sync_event_flags()));
-        if (!(dbg_events() & 4)) {
+        if ((rc = launch_resolve_setup(p, static_cast<hipStream_t>(stream), 2u))) return rc;
+        p->resolveSetupDone = true;
+        if (!p->geometryDone) BRMI_HIP(p, hipEventCreateWithFlags(&p->geometryDone, hipEventDisableTiming));
+        if (!p->frameDone) BRMI_HIP(p, hipEventCreateWithFlags(&p->frameDone, hipEventDisableTiming));
         BRMI_HIP(p, hipEventRecord(p->geometryDone, static_cast<hipStream_t>(stream)));
         BRMI_HIP(p, hipStreamWaitEvent(static_cast<hipStream_t>(shadeStream), p->geometryDone, 0));
-        }
         stream = shadeStream;
     }
     const bool lightsDone = p->lightGridDone;      // the culling pass's launches carried the light clustering
     p->lightGridDone = false;
     p->depthFinal = p->cfg.enableOcclusionCulling != 0;
     p->shadeSharesChip = split;
-    // (builds with -DBRMI_EXPERIMENTS only: debug_skip bit 0 drops the shading launch, bit 1 the G-buffer launch of brmi_execute -- what the other half costs without them)
-    static const int skipDbg = (int)experiment("debug_skip", 0);
-    rc = (skipDbg & 2) ? BRMI_OK : brmi_gbuffer(p, stream);
+    rc = brmi_gbuffer(p, stream);
     p->shadeSharesChip = false;
     p->depthFinal = false;
     if (rc) return rc;
     if (!lightsDone && (rc = brmi_light_clustering(p, stream))) return rc;
     p->shadeSharesChip = split;
-    rc = (skipDbg & 1) ? BRMI_OK : brmi_shade(p, stream);
+    rc = brmi_shade(p, stream);
     p->shadeSharesChip = false;
     if (rc) return rc;
-    if (split && !(dbg_events() & 8)) { BRMI_HIP(p, hipEventRecord(p->frameDone, static_cast<hipStream_t>(stream))); p->frameDoneRecorded = true; }
+    if (split) { BRMI_HIP(p, hipEventRecord(p->frameDone, static_cast<hipStream_t>(stream))); p->frameDoneRecorded = true; }
     p->splitFrame = false;          // (the stage entry points, called on their own, are not part of a split frame)
     return BRMI_OK;
 }
@@ -1080,10 +1046,8 @@ int brmi_debug_read_lean_queue(brmi_pass* p, uint32_t stripe, uint32_t* runs, ui
 int brmi_debug_read_bin_records(brmi_pass* p, void* dst, uint64_t bytes) {
     if (!p || !dst || !p->setupDone) return BRMI_ERR_INVALID;
     BRMI_HIP(p, hipDeviceSynchronize());
-    // (bytes with bit 63 set: the stamp region instead, where instrumented builds of k_raster park their phase sums)
-    const bool overflowRegion = (bytes >> 63) != 0; bytes &= ~(1ull << 63);
     if ((bytes >> 62) & 1ull) { bytes &= ~(1ull << 62); BRMI_HIP(p, hipMemset(p->wsPtr<uint8_t>(p->ws.binRecords), 0, bytes)); return BRMI_OK; }   // (bit 62: zero the records instead, so that a following frame's records can be told from older ones)
-    BRMI_HIP(p, hipMemcpy(dst, overflowRegion ? p->wsPtr<uint8_t>(p->ws.debugStamps) : p->wsPtr<uint8_t>(p->ws.binRecords), bytes, hipMemcpyDeviceToHost));
+    BRMI_HIP(p, hipMemcpy(dst, p->wsPtr<uint8_t>(p->ws.binRecords), bytes, hipMemcpyDeviceToHost));
     return BRMI_OK;
 }
 

@@ -44,10 +44,9 @@ struct CullArgs {
     // the few wider ones by the level-per-launch kernels (all lanes of the chip on one level); the latter skip instances narrower than this
     const uint32_t* meshLevelWidth; uint32_t levelKernelsWidthLo;
     const FlatNode* flatNodes; const FlatLeaf* flatLeaves; const InstanceWalk* instanceWalk;     // flat traversal of small hierarchies (brmi_internal.h)
-    unsigned long long* debugStamps;     // instrumented builds (-DBRMI_TILE_STAMPS)
+    uint32_t* feedback;                  // host-mapped words (brmi_pass::ensureFeedback) or null: word 2 = phase 1's bucket records (the host sizes the next frames' launches by it)
     uint32_t wideFlat;                   // phase 1: hierarchies of 257 .. 8192 nodes are k_cull_flat_wide's (the walk skips them)
     uint32_t packedFlat;                 // phase 1: the launch's first ceil(draws / 8) waves take eight draws each (hierarchies of <= 8 nodes)
-    uint32_t* feedback;                  // host-mapped words (brmi_pass::ensureFeedback) or null: word 2 = phase 1's bucket records (the host sizes the next frames' launches by it)
 };
 
 BRMI_DEV f3 to_view_space(f3 c, const m4& model, const m4& view) { return xyz(mul_vm(mul_point(c, model), view)); }
@@ -389,7 +388,6 @@ template <bool REPLAY, uint32_t HIER_CAP, uint32_t HIER_STAGE, bool SIDE = false
 // of the level kernels.  The top levels of a wide hierarchy hold a handful of nodes each; as level launches they cost 12 us apiece.
 __global__ void __launch_bounds__(64) k_cull_hierarchy(CullArgs a, BucketRecord* buckets, const uint32_t* meshLevelWidth, uint32_t widthLo, uint32_t widthHi, uint32_t spillAbove, NodeRecord* spillOut,
                                                     typename std::conditional<SIDE, SideJobs, NoSide>::type sj) {
-    wave_prio<PRIO_CULL>();
     uint32_t walkBlocks = gridDim.x;
     if constexpr (SIDE) {
         walkBlocks = sj.walkBlocks;
@@ -548,14 +546,6 @@ __global__ void __launch_bounds__(64) k_cull_hierarchy(CullArgs a, BucketRecord*
             // Same tests, same arithmetic, same records; a node is reached iff every ancestor let its children through.
             const InstanceWalk iw = a.instanceWalk[instIndex];
             if (a.packedFlat && iw.flatCount >= 1u && iw.flatCount <= 8u) continue;      // one of the eight draws of a packed wave
-#ifdef BRMI_TILE_STAMPS
-            unsigned long long hph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hprev = __builtin_amdgcn_s_memtime();
-#define HSTAMP(k) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); hph[k] += now_ - hprev; hprev = now_; } while (0)
-            { uint32_t probe_ = iw.flatCount + inst.perObjectBufferIndex; asm volatile("" :: "v"(probe_)); }
-            HSTAMP(0);
-#else
-#define HSTAMP(k) do { } while (0)
-#endif
             if (iw.flatCount > 256u && a.wideFlat) continue;      // k_cull_flat_wide's
             if (iw.flatCount != 0u && iw.flatCount <= 256u) {
                 constexpr uint32_t FLAT_CHUNKS = 4;      // 64 nodes each (brmi_set_scene: hierarchies of up to 256 nodes)
@@ -575,7 +565,6 @@ __global__ void __launch_bounds__(64) k_cull_hierarchy(CullArgs a, BucketRecord*
                     if (bad || sphere_culled(a, cam, c, r)) continue;
                     nVisible++;
                 }
-                HSTAMP(1);
                 const bool skinned = iw.skinned != 0u;
                 uint64_t preM[FLAT_CHUNKS] = {}, expandM[FLAT_CHUNKS] = {}, hiddenM[FLAT_CHUNKS] = {}, leafM[FLAT_CHUNKS] = {}, reached[FLAT_CHUNKS] = {};
                 uint32_t slabDescA[FLAT_CHUNKS] = {}, slabOffA[FLAT_CHUNKS] = {};
@@ -616,7 +605,6 @@ __global__ void __launch_bounds__(64) k_cull_hierarchy(CullArgs a, BucketRecord*
                     }
                     preM[c] = __ballot(pre); expandM[c] = __ballot(expand); hiddenM[c] = __ballot(hidden); leafM[c] = __ballot(leafOk);
                 }
-                HSTAMP(2);
                 // reached: the root, or a node that passed as a child of a reached node that lets its children through
                 reached[0] = 1ull;
                 for (bool changed = true; changed; ) {
@@ -681,10 +669,6 @@ __global__ void __launch_bounds__(64) k_cull_hierarchy(CullArgs a, BucketRecord*
                         buckets[slot] = b;
                     }
                 }
-                HSTAMP(3);
-#ifdef BRMI_TILE_STAMPS
-                if (lane < 8u) { unsigned long long v = 0; for (int k = 0; k < 8; k++) if (lane == (uint32_t)k) v = hph[k]; atomicAdd(a.debugStamps + 48u + lane, v); }
-#endif
                 continue;
             }
         }
@@ -1029,7 +1013,6 @@ __global__ void __launch_bounds__(1024) k_cull_flat_wide(CullArgs a, BucketRecor
 // the bucket records differs, which the survivor ranking (a bit per (instance, segment, meshlet)) does not see.  flatMaxDepth launches.
 template <bool FIRST>
 __global__ void __launch_bounds__(256) k_cull_flat_level(CullArgs a, uint32_t level, const NodeRecord* in, NodeRecord* out, BucketRecord* buckets) {
-    wave_prio<PRIO_CULL>();
     __shared__ uint32_t waveTot[3][4], bases[3];
     const brmi_scene_buffers& sc = a.sc;
     const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
@@ -1212,7 +1195,6 @@ struct ClearRide { uint32_t mainBlocks; ulonglong2* vis2; uint64_t n2; uint32_t 
 template <int SIDE>
 __global__ void __launch_bounds__(256) k_cull_clusters(CullArgs a, const BucketRecord* buckets, TempVisible* temp, uint32_t* bitmask, uint8_t* blockDirty,
                                                        typename std::conditional<SIDE == 1, LcRide, typename std::conditional<SIDE == 2, ClearRide, NoSide>::type>::type ride) {
-    wave_prio<PRIO_CULL>();
     uint32_t mainBlocks = gridDim.x;
     if constexpr (SIDE == 1) {
         mainBlocks = ride.mainBlocks;
@@ -1408,7 +1390,6 @@ __global__ void __launch_bounds__(256) k_scan_words(const uint32_t* bitmask, uin
 constexpr uint32_t SCAN_CHAIN_BLOCKS = 64;
 __global__ void __launch_bounds__(256) k_scan_chained(const uint32_t* bitmask, uint32_t totalWords, unsigned long long* agg, uint32_t epoch, uint32_t* wordPrefix,
                                                      uint32_t* counters, uint32_t outIndex, uint32_t capacity, uint32_t usedIndex, uint32_t* hostFeedback) {
-    wave_prio<PRIO_SCAN>();
     __shared__ uint32_t waveTotals[4];
     __shared__ uint32_t blockPrefix, ticket;
     // the block's place in the chain is the order in which blocks START (a ticket), not blockIdx: a block only ever waits for blocks that are
@@ -1476,7 +1457,6 @@ template <bool LOCAL_RANK, bool HOLD>      // HOLD: phase 1 of a frame that hold
 __global__ void __launch_bounds__(256) k_scatter_visible(const TempVisible* temp, uint32_t* counters, uint32_t tempCountIndex, const uint32_t* bitmask,
                                                         const uint32_t* wordPrefix, uint4* visible, uint32_t baseIndexCounter, uint32_t capacity, uint32_t visibleCapacity,
                                                         brmi_scene_buffers sc, ClusterSetup* setup, uint32_t resolveCapacity, ClusterUv* clusterUv, LocalRank lr, DrawLists dl) {
-    wave_prio<PRIO_SCAN>();
     const uint8_t* const* slabs = sc.slabs;
     const uint32_t n = min(counters[tempCountIndex], visibleCapacity);
     const uint32_t base = baseIndexCounter == 0xFFFFFFFFu ? 0u : counters[baseIndexCounter];
@@ -1639,7 +1619,7 @@ int launch_cull(brmi_pass* p, uint32_t phase, hipStream_t s) {
     CullArgs a;
     a.sc = p->scene; a.counters = p->counters();
     a.instanceBitBase = p->wsPtr<uint32_t>(p->ws.instanceBitBase); a.segPrefix = p->wsPtr<uint32_t>(p->ws.segPrefix);
-    a.flatNodes = p->wsPtr<FlatNode>(p->ws.flatNodes); a.flatLeaves = p->wsPtr<FlatLeaf>(p->ws.flatLeaves); a.instanceWalk = p->wsPtr<InstanceWalk>(p->ws.instanceWalk); a.debugStamps = p->wsPtr<unsigned long long>(p->ws.debugStamps);
+    a.flatNodes = p->wsPtr<FlatNode>(p->ws.flatNodes); a.flatLeaves = p->wsPtr<FlatLeaf>(p->ws.flatLeaves); a.instanceWalk = p->wsPtr<InstanceWalk>(p->ws.instanceWalk);
     a.recordCapacity = p->cfg.maxTraversalRecords; a.visibleCapacity = p->cfg.maxVisibleClusters;
     uint32_t f = p->cfg.phase2ExpansionFactor; f = f < 1 ? 1 : (f > 64 ? 64 : f);
     { uint32_t n = 1; for (uint32_t c = 2; c <= 64; c <<= 1) if (c <= f) n = c; f = n; }
@@ -1695,7 +1675,7 @@ int launch_cull(brmi_pass* p, uint32_t phase, hipStream_t s) {
         a.packedFlat = (hierarchy && !p->hostFlatNodes.empty() && p->packedFlat) ? 1u : 0u;
         // (not beside another frame's shading half: a 1024-thread workgroup with 40 KB of LDS waits long for a CU that can take it, and the
         // dense frame in flight went 0.795 -> 0.91 ms; alone the same frame's cull stage goes 0.180 -> 0.142 ms)
-        a.wideFlat = (hierarchy && p->anyWideFlat && p->wideFlat && !p->splitFrame) ? 1u : 0u;
+        a.wideFlat = (hierarchy && p->anyWideFlat && !p->splitFrame) ? 1u : 0u;
         // Scenes of very many draws (Zorah-class): the level-synchronous flat traversal, a lane per (instance, node) task, one launch per level of the
         // deepest hierarchy (k_cull_flat_level).  Its launches carry no riders: the visibility clear moves onto k_cull_clusters (ClearRide) and the
         // light clustering is launched by the frame where it finds none done.
@@ -1784,7 +1764,7 @@ int launch_cull(brmi_pass* p, uint32_t phase, hipStream_t s) {
     if (localRank) {
         // ranked inside the scatter kernel
     } else {
-        if (p->scanBlocks <= SCAN_CHAIN_BLOCKS && p->scanChained) {
+        if (p->scanBlocks <= SCAN_CHAIN_BLOCKS) {
             if (++p->scanEpoch == 0u) p->scanEpoch = 1u;
             hipLaunchKernelGGL(k_scan_chained, dim3(p->scanBlocks), dim3(256), 0, s, bitmask, p->totalWords, p->wsPtr<unsigned long long>(p->ws.scanAgg), p->scanEpoch, wordPrefix,
                                p->counters(), outIndex, p->cfg.maxVisibleClusters, usedIndex, feedback);

@@ -46,7 +46,6 @@ BRMI_DEV void hzb_tail_levels(const HzbDesc& h, uint32_t firstMip, uint32_t thre
 struct DirtyBlocks { const uint8_t* chainDirty; uint32_t chainBlocksX; };
 template <bool FROM_VIS>
 __global__ void __launch_bounds__(256) k_hzb_head(HzbDesc h, const unsigned long long* vis, float* depthOut, const uint32_t* skipUnless, uint32_t blockRow0, DirtyBlocks mk) {
-    wave_prio<PRIO_HZB>();
     if (skipUnless && *skipUnless == 0u) return;
     if (mk.chainDirty && mk.chainDirty[0] == 0u) {      // (workgroup-uniform) phase 1's values of this block's texels of the depth map and of mips 1 - 5 still stand
         if (blockIdx.x >= mk.chainBlocksX || mk.chainDirty[4u + (blockIdx.y + blockRow0) * mk.chainBlocksX + blockIdx.x] == 0u) return;
@@ -115,7 +114,6 @@ __global__ void __launch_bounds__(256) k_hzb_head(HzbDesc h, const unsigned long
 
 // `seedCounters` (brmi_execute's phase-1 build only): the block also does k_seed_phase2's work for the culling pass that follows.
 __global__ void __launch_bounds__(1024) k_hzb_tail(HzbDesc h, uint32_t firstMip, const uint32_t* skipUnless, uint32_t* seedCounters, uint32_t seedCapacity) {
-    wave_prio<PRIO_HZB>();
     if (seedCounters) seed_phase2(seedCounters, seedCapacity, threadIdx.x);      // (whatever the build does: the culling pass that follows starts from these)
     if (skipUnless && *skipUnless == 0u) return;
     hzb_tail_levels(h, firstMip, 1024u);

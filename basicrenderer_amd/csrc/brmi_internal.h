@@ -232,7 +232,7 @@ struct LayerUniform { unsigned long long coatWord, fuzzWord, coatFilledWord, fuz
 struct Workspace {     // byte offsets into BRMI_RES_WORKSPACE
     uint64_t counters, frontierA, frontierB, buckets, tempVisible, bitmask1, bitmask2, blockDirty, chainDirty, wordPrefix, blockSums,
              instanceBitBase, segPrefix, meshLevelWidth, scanAgg, flatNodes, flatLeaves, instanceWalk, planes, replayNodes, replayBuckets, lightVS, lightMeta, clusterPages, clusterHits, pageTotal, lightHitMasks, binCounts, binRecords, binOverflow, binPlan, binItems, binScratch, clusterSetup, resolveVerts, resolveTris, matWords, shadeTables, lutF, frameConst, objConst, matConst, deferredPixels,
-             frameSnapshot, debugStamps, clusterUv, binAlpha, overflowAlpha, resolveUVs, resolveColors, alphaMats, shadeRows, shadeAvgs, ggxQuads, shadeLights, clusterList, listEntries, listRecords, layerUniform,
+             frameSnapshot, clusterUv, binAlpha, overflowAlpha, resolveUVs, resolveColors, alphaMats, shadeRows, shadeAvgs, ggxQuads, shadeLights, clusterList, listEntries, listRecords, layerUniform,
              meshletBoxes, pageBoxBase, pageRefs, drawList, heldRecords, lateList, wideQueue, wideAlpha, generalList, bigQueue, bigRuns, frameClearBytes, total;
 };
 
@@ -253,7 +253,7 @@ struct brmi_pass {
     float bandPlaneTop[3] = {0, 0, 0}, bandPlaneBottom[3] = {0, 0, 0};
     uint64_t bandFirstPixel = 0, bandPixelCount = 0;   // tiled index range covering the band's tile rows
     uint32_t maxLevels = 1;
-    uint32_t spillWidth = 1024;      // meshes with a BVH level wider than this go to the level kernels below their top (<= the widest LDS frontier; BRMI_SPILL_WIDTH)
+    static constexpr uint32_t spillWidth = 1024;      // meshes with a BVH level wider than this go to the level kernels below their top (<= the widest LDS frontier)
     uint32_t spillLevels = 0;        // level-kernel launches the widest meshes still need below the point where the LDS walk hands them over
     uint32_t minLevelWidth = 0;      // narrowest such width over the meshes
     std::vector<uint32_t> hostMeshLevelWidth;   // per mesh metadata entry
@@ -303,18 +303,17 @@ struct brmi_pass {
     uint32_t phase2DirectMax = 128;   // BRMI_PHASE2_DIRECT_MAX: direct rasterisation while the last known phase-2 count is at most this (0: always bins).  Round 5: 256 -> 128 -- a camera that
                                       // moves fast leaves phase 2 two to four hundred clusters of large near triangles, which the row re-deal walks in few lanes: path_fast raster2 0.12 -> 0.065 ms
                                       // (0.648 -> 0.625 ms per frame); the slow path (30 - 80 clusters) and the still camera keep the one-launch form (sweep: profiles/r05_experiments.md)
-    uint32_t clearRiderBlocks = 8192; // single-wave workgroups of the visibility clear that ride on the traversal launch (BRMI_CLEAR_RIDER_BLOCKS)
+    static constexpr uint32_t clearRiderBlocks = 8192; // single-wave workgroups of the visibility clear that ride on the traversal launch
     bool splitFrame = false;         // brmi_execute_split with two streams: this frame's launches share the chip with another frame's
     uint32_t shadeSlabs = 0; brmi_slab_fn shadeSlabFn = nullptr; void* shadeSlabUser = nullptr;      // brmi_set_shade_slabs
     bool frameWaitsIssued = false;   // brmi_execute_split has issued this frame's cross-stream waits (the stage entry points it calls skip theirs)
-    bool wideFlat = true;            // BRMI_FLAT_WIDE=0: hierarchies of more than 256 nodes take the level walk
     bool anyWideFlat = false, allMeshesFlat = false;      // brmi_set_scene: some mesh has 257 .. 8192 nodes / every mesh has flat tables
     uint32_t flatMaxDepth = 1;       // levels of the deepest flat hierarchy (launches of the level-synchronous flat traversal, brmi_cull.hip: k_cull_flat_level)
     uint32_t flatLevelsMinDraws = 16384;   // BRMI_FLAT_LEVELS_MIN_DRAWS: scenes with at least this many draws (all hierarchies flat) take the level-synchronous flat traversal in phase 1
-    bool scanChained = true; uint32_t scanEpoch = 0;      // the survivor ranking as one launch (BRMI_SCAN_CHAINED=0: three)
+    uint32_t scanEpoch = 0;          // k_scan_chained (the survivor ranking as one launch): its block sums carry this launch count
     bool packedFlat = true;          // BRMI_FLAT_PACKED=0: one draw per wave of the traversal
-    uint32_t shadeGridShared = 10240; // workgroups of k_shade<0, 3> (BRMI_SHADE_GRID_SHARED): shorter-lived than the stand-alone 8192 so that the other frame's small geometry launches find slots sooner (Bistro-class period 6144 / 8192 / 10240 / 12288: 0.547 / 0.539 / 0.530 / 0.531 ms; Sponza-class, whose geometry half is short: 0.386 / 0.398 / 0.398 / 0.397)
-    uint32_t gbufferGridShared = 4096; // workgroups of the lean k_gbuffer in a split frame (BRMI_GBUFFER_GRID_SHARED)
+    static constexpr uint32_t shadeGridShared = 10240; // workgroups of k_shade<0, 3>: shorter-lived than the stand-alone 8192 so that the other frame's small geometry launches find slots sooner (Bistro-class period 6144 / 8192 / 10240 / 12288: 0.547 / 0.539 / 0.530 / 0.531 ms; Sponza-class, whose geometry half is short: 0.386 / 0.398 / 0.398 / 0.397)
+    static constexpr uint32_t gbufferGridShared = 4096; // workgroups of the lean k_gbuffer in a split frame
     bool shadeSharesChip = false;    // brmi_execute_split with two streams: the shading half runs beside another frame's geometry half
     bool lightGridDone = false;      // this frame's light clustering ran inside the culling pass's launches
     bool clearVisibilityWithClusterCull = false;      // brmi_execute_split on two streams: the clear rides on k_cull_clusters instead (brmi_cull.hip: ClearRide)
@@ -332,8 +331,7 @@ struct brmi_pass {
                                                          // > 8192 records of alpha-tested leaves; the overflow queues' global-atomic walk made it 1.67 ms against the others' 1.05 (1.18 now)
     uint32_t deferredStripeCapacity = 0;   // entries per deferred-pixel stripe
     uint32_t resolveCapacity = 0;   // vertices (and triangles) the resolve arena holds
-    uint32_t rasterGrid = 8192;  // single-wave workgroups of k_raster (BRMI_RASTER_GRID)
-    int rasterDebug = 0;         // BRMI_RASTER_DEBUG (experiments; non-zero gives wrong images)
+    static constexpr uint32_t rasterGrid = 8192;  // single-wave workgroups of k_raster
     int bigTriAreaDense = 32; uint32_t denseClusterCount = 6144;   // frames with that many visible clusters bin from this area on (BRMI_BIG_TRI_AREA sets both)
     int bigTriArea = 32, bigTriAreaAlpha = 32;        // clamped-bbox pixels above which a triangle is binned (BRMI_BIG_TRI_AREA; 64 until the bins kernel walked sorted slices: Sponza-class raster 0.096 -> 0.090 ms at 32)
     uint32_t hzbMipCount = 0; std::vector<uint64_t> hzbMipOffsets; std::vector<uint32_t> hzbMipW, hzbMipH;   // [mip]; offsets in floats, mip 0 unused
@@ -379,11 +377,8 @@ struct brmi_pass {
 namespace brmi {
 
 int fail(brmi_pass* p, int code, const char* fmt, ...);
-// ONE environment variable, BRMI_TUNING="key=value,key=value" (DESIGN.md 6b).  tuning(): the keys a user or a test may set (sizes that force the rare
-// paths); experiment(): keys that only exist in builds with -DBRMI_EXPERIMENTS (A/B switches of the measurements in profiles/*_experiments.md:
-// they can drop events or launches and give wrong images) -- a product build returns the default whatever the environment says.
+// ONE environment variable, BRMI_TUNING="key=value,key=value" (DESIGN.md 6b): the keys a user or a test may set (sizes that force the rare paths)
 long tuning(const char* key, long def);
-long experiment(const char* key, long def);
 #define BRMI_HIP(p, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return brmi::fail((p), BRMI_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
 #define BRMI_LAUNCH_CHECK(p, what) do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return brmi::fail((p), BRMI_ERR_HIP, "launch %s: %s", (what), hipGetErrorString(e_)); } while (0)
 

@@ -39,54 +39,32 @@ __global__ void __launch_bounds__(256) k_lc_fill(ClusterArgs a) { lc_fill_block(
 #ifndef BRMI_SHADE_WAVES
 #define BRMI_SHADE_WAVES 3
 #endif
-#ifndef BRMI_SHADE_STASH_SHARED
-#define BRMI_SHADE_STASH_SHARED 0      // floats the in-flight variant parks (experiments: 6)
-#endif
 // Round 4: the stand-alone variant (brmi_execute, the stage entry point) runs FIVE waves per SIMD: the lane index goes through an opaque copy per tile
 // (what derives from it is then recomputed where it is used instead of living in hoisted registers: 125 -> 110 VGPRs), and the next tile's G-buffer words
 // are requested behind this tile's shading instead of in front of it (-14 registers: 95 VGPRs, no scratch) -- the fifth wave hides more latency than
 // the prefetch did (serial shading 0.191 -> 0.174 ms Bistro-class, 0.182 -> 0.164 Sponza-class).  The variant that shares the chip with another frame's
 // geometry half keeps the round-3 form on purpose: at 117 VGPRs it fits four waves per SIMD, runs faster itself (0.41 -> 0.33 ms in flight) and
 // starves the geometry stream -- period 0.522 -> 0.585 ms Bistro-class (profiles/r04_experiments.md).
-#ifndef BRMI_SHADE_OPAQUE_LANE_SHARED
-#define BRMI_SHADE_OPAQUE_LANE_SHARED 0
-#endif
-#ifndef BRMI_SHADE_PREFETCH_ALONE
-#define BRMI_SHADE_PREFETCH_ALONE 0
-#endif
 #ifndef BRMI_SHADE_STASH_ALONE
 #define BRMI_SHADE_STASH_ALONE 9       // floats the stand-alone variant parks in LDS per pixel: 9 = the metal lobe's inputs, 17 = + emissive + the diffuse fit's coefficients
 #endif
 #ifndef BRMI_SHADE_WAVES_ALONE
 #define BRMI_SHADE_WAVES_ALONE 5
 #endif
-// BRMI_SHADE_SHARED_MAXWAVES (experiments): the variant that shares the chip is capped at this many waves per SIMD -- amdgpu_waves_per_eu's upper bound makes
-// the kernel descriptor claim enough registers that no more waves fit -- 0 = no cap; BRMI_SHADE_SHARED_LEAN: that variant in the stand-alone one's form
-// (opaque lane index, no prefetch: 95 VGPRs)
-#ifndef BRMI_SHADE_SHARED_MAXWAVES
-#define BRMI_SHADE_SHARED_MAXWAVES 0
-#endif
-#ifndef BRMI_SHADE_SHARED_LEAN
-#define BRMI_SHADE_SHARED_LEAN 0
-#endif
+static_assert(BRMI_SHADE_WAVES_ALONE != BRMI_SHADE_WAVES, "the two variants of k_shade<0> are told apart by their waves per SIMD");
 template <int MODE, int WAVES = BRMI_SHADE_WAVES>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE != 0 ? 1 : WAVES, (MODE == 0 && WAVES == BRMI_SHADE_WAVES && BRMI_SHADE_SHARED_MAXWAVES != 0) ? BRMI_SHADE_SHARED_MAXWAVES : 8)))
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE != 0 ? 1 : WAVES, 8)))
 k_shade(ShadeArgs a) {
-    wave_prio<PRIO_SHADE>();
-#ifndef BRMI_SHADE_SHARED_RESERVE
-#define BRMI_SHADE_SHARED_RESERVE 1
-#endif
+    constexpr bool ALONE = WAVES == BRMI_SHADE_WAVES_ALONE;
     // The variant that shares the chip holds 136 registers per wave ON PURPOSE (round 5: the arithmetic needs 123): three of its waves then leave a SIMD
     // 104 registers for the other frame's geometry waves, four waves of 128 leave none -- the shading half gets faster and the frame slower (DESIGN.md 4.6:
     // period 0.522 -> 0.585 ms when tried with a leaner kernel in round 4; 0.510 -> 0.519 in round 5).
-    if (MODE == 0 && WAVES == BRMI_SHADE_WAVES && BRMI_SHADE_WAVES_ALONE != BRMI_SHADE_WAVES && BRMI_SHADE_SHARED_RESERVE) asm volatile("" ::: "v131");
+    if (MODE == 0 && !ALONE) asm volatile("" ::: "v131");
     const ShadeFrame k = make_shade_frame(a);
     __shared__ float sliceStart[64];
     __shared__ float unormT[256];
     __shared__ float4 camK[9];                            // rows of projectionInverse, rows of viewInverse, camera position
     shade_stage_lds(a, k, sliceStart, unormT, camK);
-    constexpr bool ALONE = WAVES == BRMI_SHADE_WAVES_ALONE && BRMI_SHADE_WAVES_ALONE != BRMI_SHADE_WAVES;
-    constexpr bool OPAQUE_LANE = ALONE || BRMI_SHADE_OPAQUE_LANE_SHARED || BRMI_SHADE_SHARED_LEAN, PREFETCH = (!ALONE && !BRMI_SHADE_SHARED_LEAN) || (ALONE && BRMI_SHADE_PREFETCH_ALONE);
     if (MODE == 0) {
         // One 8x8 tile per wave and iteration: the tile index is wave-uniform, so the base address of every plane is scalar arithmetic and a
         // lane only adds its own constant offset (no per-lane 64-bit address math, no integer division per pixel).  Software pipeline: the
@@ -94,9 +72,6 @@ k_shade(ShadeArgs a) {
         const uint32_t lane = threadIdx.x & 63u;
         const uint32_t wavesInGrid = gridDim.x * (blockDim.x >> 6);
         const uint32_t tileCount = (uint32_t)((a.pixelCount + 63ull) >> 6), firstTile = (uint32_t)(a.firstPixel >> 6);
-#ifndef BRMI_SHADE_TILE_RUNS
-#define BRMI_SHADE_TILE_RUNS 1
-#endif
         // Round 5: a wave takes a RUN of neighbouring tiles (tiles per wave = ceil(tiles / waves) of them, left to right) instead of every
         // `wavesInGrid`-th tile of the band.  A light cluster of the 12 x 12 grid is 40 tiles wide at 4K, so the tiles of a run sit in one cluster nearly
         // always: the list head and the 64 B light records the first tile fetched through the scalar cache (16 KB) are still there for the others.  Strided,
@@ -105,18 +80,17 @@ k_shade(ShadeArgs a) {
         const uint32_t waveInGrid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
         // (the stand-alone variant only: 0.1665 -> 0.1635 ms; beside another frame's geometry half the strided order is 2 % better -- tiles of one
         // workgroup then end at different times and slots come free more evenly: Bistro-class 0.504 against 0.514 ms per frame, Sponza-class 0.388 / 0.397)
-        constexpr bool RUNS = BRMI_SHADE_TILE_RUNS && ALONE;
-        const uint32_t run = RUNS ? (tileCount + wavesInGrid - 1u) / wavesInGrid : 1u;
-        uint32_t t = RUNS ? waveInGrid * run : waveInGrid;
-        const uint32_t tEnd = RUNS ? min(t + run, tileCount) : tileCount;
+        const uint32_t run = ALONE ? (tileCount + wavesInGrid - 1u) / wavesInGrid : 1u;
+        uint32_t t = ALONE ? waveInGrid * run : waveInGrid;
+        const uint32_t tEnd = ALONE ? min(t + run, tileCount) : tileCount;
         uint32_t tx = (firstTile + t) % a.tilesX, ty = (firstTile + t) / a.tilesX;
-        const uint32_t stepX = RUNS ? 1u : wavesInGrid % a.tilesX, stepY = RUNS ? 0u : wavesInGrid / a.tilesX;
-        const uint32_t stepT = RUNS ? 1u : wavesInGrid;
+        const uint32_t stepX = ALONE ? 1u : wavesInGrid % a.tilesX, stepY = ALONE ? 0u : wavesInGrid / a.tilesX;
+        const uint32_t stepT = ALONE ? 1u : wavesInGrid;
         // (the lane index behind an opaque copy per tile: its row / column inside the tile and the byte offsets of the plane loads are then a VALU
         // instruction each where they are used, not loop invariants in registers of their own -- the trick that took the G-buffer kernel from 73 to 59 VGPRs)
         auto fetch = [&](uint32_t tt, uint32_t ttx, uint32_t tty, bool& ok) {
             uint32_t ln = lane;
-            if (OPAQUE_LANE) asm volatile("" : "+v"(ln));
+            if (ALONE) asm volatile("" : "+v"(ln));
             const uint32_t px = ttx * 8u + (ln >> 3), py = tty * 8u + (ln & 7u);
             ok = tt < tEnd && px < a.W && py < a.H && py >= a.bandY0 && py < a.bandY1;
             return ok ? load_raw_pixel_plain(a, ((uint64_t)(firstTile + tt) << 6), ln, px, py) : empty_raw_pixel();
@@ -128,13 +102,13 @@ k_shade(ShadeArgs a) {
             if (ntx >= a.tilesX) { ntx -= a.tilesX; nty++; }
             bool nok = false;
             RawPixel nxt = empty_raw_pixel();
-            if (PREFETCH) nxt = fetch(nt, ntx, nty, nok);
+            if (!ALONE) nxt = fetch(nt, ntx, nty, nok);
             const uint64_t tileBase = (uint64_t)(firstTile + t) << 6;
             uint32_t ls = lane;
-            if (OPAQUE_LANE) asm volatile("" : "+v"(ls));
-            const uint32_t cls = shade_pixel<0, (BRMI_SHADE_METAL_STASH && WAVES == BRMI_SHADE_WAVES_ALONE && BRMI_SHADE_WAVES_ALONE != BRMI_SHADE_WAVES) ? BRMI_SHADE_STASH_ALONE : BRMI_SHADE_STASH_SHARED>(a, k, sliceStart, unormT, camK, cur, ok, tileBase, ls);
+            if (ALONE) asm volatile("" : "+v"(ls));
+            const uint32_t cls = shade_pixel<0, ALONE ? BRMI_SHADE_STASH_ALONE : 0>(a, k, sliceStart, unormT, camK, cur, ok, tileBase, ls);
             shade_defer(a, t, cls, ls);
-            if (!PREFETCH) nxt = fetch(nt, ntx, nty, nok);      // (experiments: the next tile's words requested behind this tile's shading, ~14 registers less in it)
+            if (ALONE) nxt = fetch(nt, ntx, nty, nok);      // (the stand-alone variant: the next tile's words requested behind this tile's shading, ~14 registers less in it)
             cur = nxt; ok = nok; t = nt; tx = ntx; ty = nty;
         }
     } else {
@@ -266,11 +240,8 @@ static int launch_shade_range(brmi_pass* p, hipStream_t s, uint32_t row0, uint32
     // 8192 workgroups of four waves, four tiles per wave at 4K: against 4096 (eight tiles per wave) the kernel's tail is shorter (233 -> 226 us)
     // and, with another frame's geometry half in flight beside it, slots come free twice as often for that half's high-priority launches
     // (Bistro 4K, two frames in flight: 0.436 -> 0.413 ms per frame; 16384: 0.425, 2048: 0.49)
-    {
-        static const uint32_t pad = (uint32_t)experiment("shade_lds_pad", 0);   // (builds with -DBRMI_EXPERIMENTS: unused dynamic LDS caps the kernel's occupancy)
-        if (p->shadeSharesChip || BRMI_SHADE_WAVES_ALONE == BRMI_SHADE_WAVES) hipLaunchKernelGGL((k_shade<0, BRMI_SHADE_WAVES>), dim3(std::max(256u, p->shadeGridShared / share)), dim3(256), pad, s, a);
-        else hipLaunchKernelGGL((k_shade<0, BRMI_SHADE_WAVES_ALONE>), dim3(std::max(256u, 8192u / share)), dim3(256), pad, s, a);
-    }
+    if (p->shadeSharesChip) hipLaunchKernelGGL((k_shade<0, BRMI_SHADE_WAVES>), dim3(std::max(256u, p->shadeGridShared / share)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_shade<0, BRMI_SHADE_WAVES_ALONE>), dim3(std::max(256u, 8192u / share)), dim3(256), 0, s, a);
     // deferred pixels by class: coat, fuzz, both -- only the variants some material of the scene can need
     if (p->sceneHasCoat) hipLaunchKernelGGL(k_shade<1>, dim3(512), dim3(256), 0, s, a);
     if (p->sceneHasFuzz) hipLaunchKernelGGL(k_shade<2>, dim3(512), dim3(256), 0, s, a);

@@ -49,9 +49,6 @@ constexpr int BIN_W = 256, BIN_ROWS = 16;          // bin = 4096 keys = 32 KB of
 constexpr int BIN_W_SHIFT = 8, BIN_ROWS_SHIFT = 4;
 // a bin's record counter has a 128 B line to itself: atomics on ONE cache line serialise at 50-90 per microsecond whatever their addresses, and
 // the bins of a screen band (15 neighbours in one line, the horizon's among them) take thousands of slot reservations per frame
-#ifndef BRMI_CHAIN_DIRTY_BLOCKS
-#define BRMI_CHAIN_DIRTY_BLOCKS 1      // phase 2 records the 32 x 32 px blocks it may touch; the second depth-chain build redoes only those
-#endif
 constexpr uint32_t BIN_COUNT_STRIDE = BRMI_BIN_COUNT_STRIDE;
 constexpr int BIN_WINDOW = 256;                     // bins a wave counts in LDS with its reservations held in registers (cells of its bin bounding box)
 constexpr int COOP_ENTRIES = 64;                    // triangles with more bin entries than this are emitted by the whole wave ...
@@ -85,7 +82,6 @@ struct RasterArgs {
     // the plan of a k_raster_bins launch (plan_bins): header {itemCount, ticket}, per bin {records, first scratch tile, slices done}, the work items
     uint32_t tableCells;     // k_raster: words of dynamic LDS behind the launch (>= BIN_WINDOW): the LDS window a wave counts its records per bin in
     uint32_t* binPlan; uint32_t* binItems; unsigned long long* binScratch; uint32_t binScratchTiles, binItemCapacity;
-    int debugFlags;          // experiments only (BRMI_RASTER_DEBUG): 1 = skip the direct walk, 2 = skip bin emission, 4 = skip the bin pass, 8 = direct walk without the atomic
     brmi_scene_buffers sc;
     const uint4* clusters; const ClusterSetup* setup;
     uint32_t* counters;
@@ -104,7 +100,6 @@ struct RasterArgs {
     uint32_t visW, visH, tilesX, bandY0, bandY1;      // visW x visH: the FRAME (scissor clamp); bandY0 / bandY1: rows of the surface this GPU renders (records live in surface rows)
     uint32_t rowLo, rowHi;                            // frame rows k_raster looks at: the band, or the whole frame with the interleaved partition ...
     StripeMap stripes;                                // ... whose ownership test and frame row -> surface row mapping this is
-    unsigned long long* debugStamps;                     // instrumented builds only
 };
 
 // `frameState` (may be null): the counters + survivor bitmasks block that the culling pass clears at the start of a frame; brmi_execute
@@ -131,9 +126,8 @@ BRMI_DEV void clip_scanline(float value, float step, int& first, int& last, bool
 // Where a key goes: the visibility buffer (tiled, 64-bit atomic min in L2) or the LDS tile of a bin.
 struct GlobalSink {
     static constexpr bool kPeekCheap = false;
-    unsigned long long* vis; uint32_t tilesX; int dbg;
+    unsigned long long* vis; uint32_t tilesX;
     BRMI_DEV void operator()(int px, int py, unsigned long long key) const {
-        if (dbg & 8) { if (key == 0x1234567ull) vis[0] = key; return; }
         atomicMin(&vis[tiled_index((uint32_t)px, (uint32_t)py, tilesX)], key);
     }
     BRMI_DEV unsigned long long peek(int px, int py) const { return __builtin_nontemporal_load(&vis[tiled_index((uint32_t)px, (uint32_t)py, tilesX)]); }
@@ -245,7 +239,7 @@ BRMI_DEV SegWalk seg_begin(int minX, int rectWidth, bool useScanlineRanges, floa
 // Stores one record at a reserved slot of a bin; when the bin is full its rows are rasterised here with global atomics (counted).
 template <typename Alpha>
 BRMI_DEV void raster_record_global(const RasterArgs& a, const BinRecord& r, const Alpha& alpha, uint32_t strip, uint32_t firstRow, uint32_t rowStep) {
-    const GlobalSink sink{a.vis, a.tilesX, 0};
+    const GlobalSink sink{a.vis, a.tilesX};
     const uint32_t n = (r.triAndFlags >> 16) & 0xFFu;
     float sb0 = r.sb0, sb1 = r.sb1;
     uint32_t k = 0;
@@ -309,7 +303,6 @@ BRMI_DEV void bin_append(const RasterArgs& a, const float* unorm, const BinRecor
 template <bool ALPHA, bool LEAN = false>
 __global__ void __launch_bounds__(64, LEAN ? BRMI_RASTER_LEAN_WAVES : (ALPHA ? BRMI_RASTER_ALPHA_WAVES : BRMI_RASTER_WAVES)) k_raster(RasterArgs a) {
     static_assert(!(ALPHA && LEAN), "the lean form has no alpha test");
-    wave_prio<PRIO_RASTER>();
     // (one wave per workgroup: LDS hand-offs between its lanes need wave_lds_sync() only.  __syncthreads() also waits for every global store
     // and atomic the wave has in flight -- the record stores and the small boxes' atomic-mins: a memory round trip per hand-off.)
     __shared__ float sx[BRMI_MESHLET_MAX_VERTS], sy[BRMI_MESHLET_MAX_VERTS], sd[BRMI_MESHLET_MAX_VERTS];
@@ -322,19 +315,13 @@ __global__ void __launch_bounds__(64, LEAN ? BRMI_RASTER_LEAN_WAVES : (ALPHA ? B
     __shared__ int tpI[4][64];
     __shared__ uint32_t rowOff[65];
     const brmi_scene_buffers& sc = a.sc;
-    const uint32_t lane0 = threadIdx.x;
-#ifndef BRMI_RASTER_OPAQUE_LANE
-#define BRMI_RASTER_OPAQUE_LANE 0
-#endif
-#if !BRMI_RASTER_OPAQUE_LANE
-    const uint32_t lane = lane0;
-#endif
+    const uint32_t lane = threadIdx.x;
     // wave-uniform by construction; said so to the compiler, which then fetches a cluster's records with scalar loads (one s_load per record
     // instead of a chain of vector loads with a wait after each: the fetch was 11-29 % of the kernel's wave-cycles, measured with phase stamps)
     const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.firstCounter == 0xFFFFFFFFu ? 0u : a.counters[a.firstCounter]));
     const uint32_t count = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.counters[a.countCounter]);
-    if (a.countFeedback && blockIdx.x == 0u && lane0 == 0u) __hip_atomic_store(a.countFeedback, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    const GlobalSink gsink{a.vis, a.tilesX, a.debugFlags};
+    if (a.countFeedback && blockIdx.x == 0u && lane == 0u) __hip_atomic_store(a.countFeedback, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    const GlobalSink gsink{a.vis, a.tilesX};
     // static round-robin over clusters: a shared queue head saturates at ~90 dequeues/us (MI355X_MICROARCH.md, row
     // "dequeue"), which is slower than the work itself once big triangles are handed off
     // Frames with far fewer clusters than the grid has waves (every BASELINE-class frame: ~2 k clusters on 1024 SIMDs) are bound by a
@@ -347,15 +334,9 @@ __global__ void __launch_bounds__(64, LEAN ? BRMI_RASTER_LEAN_WAVES : (ALPHA ? B
     // clusters with large near triangles, where a cluster is 20 k bin records from one wave, takes two waves per cluster: raster 0.345 -> 0.32 ms at position
     // 20 of the bench's path; a Sponza-class frame of 1.5 k clusters keeps four per cluster, eight cost it 10 us.  A larger grid does the same for the
     // rasteriser alone, but 8,192 more waves that find nothing each wait for a slot beside the other frame's shading waves.)
-    if (!LEAN && !(a.debugFlags & 0x40000000u)) { while (split < 8u && count * split * 2u <= (split == 1u ? BRMI_RASTER_SPLIT_FIRST * gridDim.x : gridDim.x)) split *= 2u; }
+    if (!LEAN) { while (split < 8u && count * split * 2u <= (split == 1u ? BRMI_RASTER_SPLIT_FIRST * gridDim.x : gridDim.x)) split *= 2u; }
     const uint32_t parts = max(split >> 1, 1u), lanesPerPart = 64u / parts;      // shares of a pass
     const uint32_t items = count * split;
-#ifdef BRMI_TILE_STAMPS
-    unsigned long long kph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, kprev = __builtin_amdgcn_s_memtime();
-#define KSTAMP(k) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); kph[k] += now_ - kprev; kprev = now_; } while (0)
-#else
-#define KSTAMP(k) do { } while (0)
-#endif
     // Alpha-tested pixels of the small boxes (round 4, as in k_raster_bins<true>): the row walk only finds covered pixels and appends them (key,
     // texcoord, pixel, material) to this ring; whenever 64 are waiting the wave looks at the visibility buffer and samples for all of them at once --
     // every lane busy in the sampler instead of the few whose row has a covered pixel at that step.  The ring lives across batches and clusters; what
@@ -367,8 +348,8 @@ __global__ void __launch_bounds__(64, LEAN ? BRMI_RASTER_LEAN_WAVES : (ALPHA ? B
     uint32_t rqHead = 0, rqTail = 0;      // wave-uniform
     auto rq_drain = [&](uint32_t n) {
         wave_lds_sync();
-        if (lane0 < n) {
-            const uint32_t e = (rqHead + lane0) & (RQ - 1u);
+        if (lane < n) {
+            const uint32_t e = (rqHead + lane) & (RQ - 1u);
             const unsigned long long key = rqKey[e];
             const int px = (int)(rqPix[e] & 0xFFFFu), py = (int)(rqPix[e] >> 16);
             const AlphaMaterial m = a.alphaMats[rqMat[e]];
@@ -384,10 +365,6 @@ __global__ void __launch_bounds__(64, LEAN ? BRMI_RASTER_LEAN_WAVES : (ALPHA ? B
     // entry is requested while this one is walked: one SGPR, unlike the 16 of the whole record that cost more than they saved in round 5)
     uint32_t listed = (a.drawList && blockIdx.x < items) ? kconst(a.drawList)[first + blockIdx.x / split] : 0u;
     for (uint32_t item = blockIdx.x; item < items; item += gridDim.x) {
-#if BRMI_RASTER_OPAQUE_LANE
-        uint32_t lane = lane0; asm volatile("" : "+v"(lane));      // (what a cluster derives from the lane index is recomputed per cluster, not hoisted into registers and SGPR spill lanes)
-#endif
-        KSTAMP(7);
         const uint32_t c = item / split, sub = item % split;
         const uint32_t clusterIndex = a.drawList ? (uint32_t)__builtin_amdgcn_readfirstlane((int)listed) : first + c;
         if (a.drawList && item + gridDim.x < items) listed = kconst(a.drawList)[first + (item + gridDim.x) / split];
@@ -426,8 +403,6 @@ __global__ void __launch_bounds__(64, LEAN ? BRMI_RASTER_LEAN_WAVES : (ALPHA ? B
         AlphaMaterial amat{};
         if (alphaCluster) { cu = a.clusterUv[clusterIndex]; amat = a.alphaMats[cs.materialDataIndex]; }
 
-        if (a.debugFlags & 0x100) { const float probe_ = mvp.m[0][0] + modelViewZ.x + visWidth; if (probe_ == 1234.5f) a.counters[CNT_DROPPED_CLUSTERS] = 1u; }   // (instrumented runs: the cluster's records have arrived)
-        KSTAMP(0);
         // vertex stage -> LDS (softwareRaster.hlsl:339-387)
         if (!toGeneral)
         for (uint32_t v = lane; v < vertCount; v += 64) {
@@ -452,7 +427,6 @@ __global__ void __launch_bounds__(64, LEAN ? BRMI_RASTER_LEAN_WAVES : (ALPHA ? B
             if (alphaCluster) { const f2 uv = decode_uv(cu, v); siw[v] = invW; su[v] = uv.x; sv[v] = uv.y; }
         }
         wave_lds_sync();
-        KSTAMP(1);
 
         // triangle stage: lane = triangle (softwareRaster.hlsl:416-611)
         for (uint32_t waveBase = passLo; waveBase < passHi && !toGeneral; waveBase += 64) {
@@ -575,7 +549,7 @@ __global__ void __launch_bounds__(64, LEAN ? BRMI_RASTER_LEAN_WAVES : (ALPHA ? B
             // instead of being emitted one at a time by the whole wave.
             // (round 6: with the wide pass behind this launch the limit is that pass's -- its emission is a workgroup's, a lane's is one record after the other)
             const int coopEntries = a.wideQueue ? (int)a.wideEntries : (a.tableCells > (uint32_t)BIN_WINDOW ? COOP_ENTRIES_TABLE : COOP_ENTRIES);
-            const bool few = entries > 0 && entries <= coopEntries && !(a.debugFlags & 2);
+            const bool few = entries > 0 && entries <= coopEntries;
             bool fewW = few;      // (a pass whose bins fit no window falls back to the 64-entry rule below)
             const bool anyFew = __any(few);
             int wb0 = 0, ws0 = 0, winW = 1, cells = 0; bool windowed = false, wideWindow = false;
@@ -606,21 +580,17 @@ __global__ void __launch_bounds__(64, LEAN ? BRMI_RASTER_LEAN_WAVES : (ALPHA ? B
                     }
                 }
             }
-            KSTAMP(2);
             // Small boxes: global atomics.  lane = triangle leaves most lanes idle (culled triangles, boxes of very different
             // size), so the rows of the batch's small triangles are re-dealt to the lanes: an exclusive scan of the row counts,
             // the setup of every triangle parked in LDS, then lane k takes rows k, k + 64, ... of the concatenated row list.
 #ifndef BRMI_RASTER_TINY
 #define BRMI_RASTER_TINY 4
 #endif
-#ifndef BRMI_RASTER_TINY_RANGES
-#define BRMI_RASTER_TINY_RANGES 0
-#endif
             // Round 5: a pass whose small boxes are ALL at most BRMI_RASTER_TINY x BRMI_RASTER_TINY pixels (frames of sub-pixel triangles: the Zorah-class frame rasterises 62 M
             // triangles for 33 M pixels) is walked lane = triangle -- no prefix scan, no parking of thirteen values per triangle in LDS, no bisection per row task: the re-deal
             // exists to balance boxes of very different size, and these are all the same.  Same arithmetic per pixel (raster_row from the box's first row).
-            const bool smallHere = active && !bigHere && !(a.debugFlags & 1) && yLo <= yHi;
-            const bool tinyPass = BRMI_RASTER_TINY > 0 && !striped && !alphaCluster && (BRMI_RASTER_TINY_RANGES || !useScanlineRanges) && !__any(smallHere && (maxY - minY + 1) > BRMI_RASTER_TINY);
+            const bool smallHere = active && !bigHere && yLo <= yHi;
+            const bool tinyPass = BRMI_RASTER_TINY > 0 && !striped && !alphaCluster && !useScanlineRanges && !__any(smallHere && (maxY - minY + 1) > BRMI_RASTER_TINY);
             if (tinyPass) {
                 if (smallHere) {
                     float sb0 = row_b0, sb1 = row_b1;
@@ -705,7 +675,6 @@ __global__ void __launch_bounds__(64, LEAN ? BRMI_RASTER_LEAN_WAVES : (ALPHA ? B
                     wave_lds_sync();
                 }
             }
-            KSTAMP(3);
             // the records of triangles with a few bins: slots handed out from the runs reserved above
             if (anyFew) {
                 if (windowed && !wideWindow) {
@@ -750,12 +719,11 @@ __global__ void __launch_bounds__(64, LEAN ? BRMI_RASTER_LEAN_WAVES : (ALPHA ? B
                 }
                 if (windowed) wave_lds_sync();    // binBase is reused by the next batch
             }
-            if (anyFew && !windowed) KSTAMP(6); else KSTAMP(4);      // (instrumented builds: passes whose bins do not fit the LDS window reserve slot by slot)
             // many bins: the whole wave emits the triangle.  lane L owns bands band0 + L, band0 + L + 64, ...: it steps the row
             // start down to each of them (the same additions the serial loop makes) and appends the band's record to every strip.
-            const bool isCoop = entries > 0 && !fewW && !(a.debugFlags & 2);
+            const bool isCoop = entries > 0 && !fewW;
             uint64_t coop = __ballot(isCoop);
-            const bool wideCand = entries > (int)a.wideEntries && !(a.debugFlags & 2);      // (with the queue on these are exactly the triangles `few` left out)
+            const bool wideCand = entries > (int)a.wideEntries;      // (with the queue on these are exactly the triangles `few` left out)
             const uint64_t candM = __ballot(wideCand);
             if (candM != 0ull) {
                 // round 6: these go to the wide queue (one reservation per wave); what does not fit -- or all of them, when the host has not launched the wide pass for this
@@ -812,20 +780,11 @@ __global__ void __launch_bounds__(64, LEAN ? BRMI_RASTER_LEAN_WAVES : (ALPHA ? B
                     }
                 }
             }
-            KSTAMP(5);
         }
         if (LEAN && toGeneral && lane == 0u) a.generalList[atomicAdd(&a.counters[a.generalCounter], 1u)] = clusterIndex;
         wave_lds_sync();   // LDS is reused by the next cluster
     }
     if (ALPHA && rqTail != rqHead) rq_drain(rqTail - rqHead);
-#ifdef BRMI_TILE_STAMPS
-    if (lane0 < 8u && (a.debugFlags & 0x100)) { unsigned long long v = 0; for (int k = 0; k < 8; k++) if (lane0 == (uint32_t)k) v = kph[k]; atomicAdd(a.debugStamps + 16u + lane0, v); }
-    if (lane0 == 0u && (a.debugFlags & 0x100)) {      // the launch's longest wave: its cycles per phase (slots 40 .. 47), kept by a 64-bit max on its total (slot 48)
-        unsigned long long tot = 0; for (int k = 0; k < 8; k++) tot += kph[k];
-        const unsigned long long before = atomicMax(a.debugStamps + 48u, tot);
-        if (tot > before) for (int k = 0; k < 8; k++) a.debugStamps[40 + k] = kph[k];      // (racy between near-equal waves: a diagnostic)
-    }
-#endif
 }
 
 // The lean rasteriser's binned triangles (RasterArgs::bigQueue), 64 queue entries per wave and step: the record emission of k_raster on its own -- per-bin counts in
@@ -833,7 +792,6 @@ __global__ void __launch_bounds__(64, LEAN ? BRMI_RASTER_LEAN_WAVES : (ALPHA ? B
 // go on to the wide queue.  Consecutive entries are triangles of one cluster (a wave of k_raster<false, true> appends a pass's triangles together), so a wave's bins
 // are as few as they were there.  Records, and so keys, as k_raster writes them.
 __global__ void __launch_bounds__(64) k_raster_emit(RasterArgs a) {
-    wave_prio<PRIO_RASTER>();
     extern __shared__ uint32_t binBase[];          // a.tableCells words
     const uint32_t lane = threadIdx.x;
     const uint32_t stripe = blockIdx.x & 63u;
@@ -847,9 +805,6 @@ __global__ void __launch_bounds__(64) k_raster_emit(RasterArgs a) {
         w.pad[0] = w.pad[1] = w.pad[2] = 0u;      // (what the writer stored there; said here so that the three words are not carried -- in scratch -- to the wide queue's store)
         const int nStrips = w.strip1 - w.strip0 + 1;
         int entries = have ? (w.band1 - w.band0 + 1) * nStrips : 0;
-#ifdef BRMI_EXPERIMENTS
-        if (a.debugFlags & 0x200) { if (w.base.sb0 == 1234.5f && w.yHi == -77) a.counters[CNT_DROPPED_CLUSTERS] = 1u; entries = 0; }      // (timing runs: the entries have arrived, nothing is emitted)
-#endif
         // (the wide pass takes this kernel's triangles from 16 entries on, not 128: a lane's records are emitted one after the other and the launch lasts as long as its longest
         // lane -- 144 us at 128, 73 at 16, 61 at 8 for the Zorah-class frame's 573 k queued triangles, k_raster_wide 22 us either way; profiles/r06_experiments.md)
         const int coopEntries = a.wideQueue ? (int)a.emitWideEntries : (a.tableCells > (uint32_t)BIN_WINDOW ? COOP_ENTRIES_TABLE : COOP_ENTRIES);
@@ -884,9 +839,6 @@ __global__ void __launch_bounds__(64) k_raster_emit(RasterArgs a) {
                 }
                 wave_lds_sync();
             }
-#ifdef BRMI_EXPERIMENTS
-            if (a.debugFlags & 0x400) { if (windowed) wave_lds_sync(); continue; }      // (timing runs: counted and reserved, no record stored)
-#endif
             if (fewW) {
                 // step the row start band by band (the additions of the serial loop) and append one record per band and strip
                 float sb0 = w.base.sb0, sb1 = w.base.sb1;
@@ -957,7 +909,6 @@ __global__ void __launch_bounds__(64) k_raster_emit(RasterArgs a) {
 constexpr uint32_t WIDE_SHARES = 8;
 template <bool ALPHA>
 __global__ void __launch_bounds__(64) k_raster_wide(RasterArgs a) {
-    wave_prio<PRIO_RASTER>();
     __shared__ float unormT[ALPHA ? 256 : 1];
     if (ALPHA) { for (uint32_t i = threadIdx.x; i < 256u; i += 64u) unormT[i] = (float)i / 255.0f; __syncthreads(); }
     const uint32_t n = min(a.counters[a.wideCounter], a.wideCapacity);
@@ -1012,12 +963,6 @@ __global__ void __launch_bounds__(64) k_raster_wide(RasterArgs a) {
 #ifndef BRMI_BIN_THREADS
 #define BRMI_BIN_THREADS 512
 #endif
-#ifndef BRMI_BIN_PRIORITY
-#define BRMI_BIN_PRIORITY 0
-#endif
-#ifndef BRMI_BIN_SORT
-#define BRMI_BIN_SORT 1
-#endif
 #ifndef BRMI_BIN_SORT_MIN
 #define BRMI_BIN_SORT_MIN 96u
 #endif
@@ -1034,7 +979,6 @@ constexpr uint32_t BIN_ORDER_CAP = 1024;       // longest slice the walk order i
 #endif
 template <bool ALPHA>
 __global__ void __launch_bounds__(BRMI_BIN_THREADS, ALPHA ? BRMI_BIN_ALPHA_WAVES : 1) k_raster_bins(RasterArgs a) {
-    wave_prio<PRIO_BINS>();
     __shared__ unsigned long long tile[BIN_W * BIN_ROWS];
     __shared__ float unormT[ALPHA ? 256 : 1];
 #ifndef BRMI_ALPHA_SEG_SHIFT
@@ -1046,9 +990,6 @@ __global__ void __launch_bounds__(BRMI_BIN_THREADS, ALPHA ? BRMI_BIN_ALPHA_WAVES
     __shared__ uint32_t taskStart[ALPHA ? ALPHA_LIST + 1 : 1];      // exclusive prefix of the listed records' task counts
     __shared__ uint32_t scanPart[ALPHA ? 2 * BRMI_BIN_THREADS / 64 : 1];      // the waves' sums of the task scan
     __shared__ uint32_t taskNext, rowNext;
-#ifndef BRMI_ALPHA_COMPACT
-#define BRMI_ALPHA_COMPACT 1
-#endif
     // pixels of alpha-tested records that are covered and can still win their key, waiting for the test: a ring per wave (see the task pass)
 // (64 entries: with the 1024-record task lists the workgroup needs 50 KB of LDS and 80 VGPRs -- three workgroups per CU, six waves per SIMD, instead of two and four
     // with 128 entries and 2048 records: San-Miguel-class raster stage 0.265 -> 0.245 ms, frame in flight 0.867 -> 0.838.  A step that would overflow the ring tests what
@@ -1056,7 +997,7 @@ __global__ void __launch_bounds__(BRMI_BIN_THREADS, ALPHA ? BRMI_BIN_ALPHA_WAVES
 #ifndef BRMI_ALPHA_RING
 #define BRMI_ALPHA_RING 64
 #endif
-    constexpr uint32_t AQ = BRMI_ALPHA_RING, AQ_WAVES = (ALPHA && BRMI_ALPHA_COMPACT) ? BRMI_BIN_THREADS / 64 : 1, AQ_N = (ALPHA && BRMI_ALPHA_COMPACT) ? AQ : 1;
+    constexpr uint32_t AQ = BRMI_ALPHA_RING, AQ_WAVES = ALPHA ? BRMI_BIN_THREADS / 64 : 1, AQ_N = ALPHA ? AQ : 1;
     __shared__ unsigned long long qKey[AQ_WAVES][AQ_N];
     __shared__ float qU[AQ_WAVES][AQ_N], qV[AQ_WAVES][AQ_N];
     __shared__ uint32_t qMeta[AQ_WAVES][AQ_N];
@@ -1069,17 +1010,10 @@ __global__ void __launch_bounds__(BRMI_BIN_THREADS, ALPHA ? BRMI_BIN_ALPHA_WAVES
     // last folds the others' tiles into its own and merges once, plainly -- no per-key atomics (as atomic-min merges, eight keys of a 64 B line
     // from several slices at a time, slices shorter than 1024 records LOST: raster 0.22 -> 0.25 -> 0.29 ms at 512 / 256).
     // Why a list: a grid of (bins x slices) workgroups started in grid order; a slice of 1024 records that started 30 us into the launch ended
-    // it at 126 us while the balanced load was 56 us, and 14,000 of the 16,200 workgroups found nothing (tools/bins_timeline.py).
+    // it at 126 us while the balanced load was 56 us, and 14,000 of the 16,200 workgroups found nothing.
     __shared__ uint32_t curItem, doneBefore;
     const uint32_t itemCount = min(a.binPlan[0], a.binItemCapacity), nBins = a.binsX * a.binsY;
     const uint32_t* binN = a.binPlan + 16, * binSlot = binN + nBins; uint32_t* binDone = a.binPlan + 16 + 2u * nBins;
-#ifdef BRMI_TILE_STAMPS
-    unsigned long long bph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bprev = __builtin_amdgcn_s_memtime();
-    unsigned long long wWait = 0, wWalk = 0, wPrev = 0;
-#define BSTAMP(k) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); bph[k] += now_ - bprev; bprev = now_; } while (0)
-#else
-#define BSTAMP(k) do { } while (0)
-#endif
     if (ALPHA) for (uint32_t i = threadIdx.x; i < 256u; i += BRMI_BIN_THREADS) unormT[i] = (float)i / 255.0f;
     // Items are handed out by ticket, in list order.  An atomic with return on one address serves ~90 per microsecond, so a thousand workgroups
     // asking at once would wait up to 11 us for their first item: the first half of the pool starts on the item of its own index instead.  (Not
@@ -1098,9 +1032,6 @@ __global__ void __launch_bounds__(BRMI_BIN_THREADS, ALPHA ? BRMI_BIN_ALPHA_WAVES
     // alpha variant spilled ten such loop invariants)
     uint32_t tid = threadIdx.x;
     if (ALPHA) asm volatile("" : "+v"(tid));
-#ifdef BRMI_TILE_STAMPS
-    const unsigned long long wgStart = __builtin_amdgcn_s_memrealtime();      // 100 MHz, the same clock on every CU: a timeline of the launch's items
-#endif
     const uint32_t item = a.binItems[itemIndex];
     const uint32_t bin = item & 0xFFFFu, slice = (item >> 16) & 0xFFu, sliceCount = (item >> 24) + 1u;
     const uint32_t strip = bin % a.binsX, band = bin / a.binsX;
@@ -1113,7 +1044,6 @@ __global__ void __launch_bounds__(BRMI_BIN_THREADS, ALPHA ? BRMI_BIN_ALPHA_WAVES
     if (ALPHA && tid == 0) { taskNext = 0u; rowNext = 0u; }
     for (uint32_t i = tid; i < BIN_W * BIN_ROWS; i += BRMI_BIN_THREADS) tile[i] = BRMI_VIS_EMPTY;
     __syncthreads();
-    BSTAMP(0);
     const int x0 = (int)(strip << BIN_W_SHIFT), y0 = (int)(band << BIN_ROWS_SHIFT);
     const LdsSink sink{tile, x0, y0};
     const BinRecord* recs = a.binRecords + (size_t)bin * a.binCapacity;
@@ -1124,7 +1054,7 @@ __global__ void __launch_bounds__(BRMI_BIN_THREADS, ALPHA ? BRMI_BIN_ALPHA_WAVES
     // record gets 4, 8 or 16 lanes, and the records a wave takes together are about equally wide.  Keys are order-free (64-bit min).
     constexpr uint32_t WIDTH_CLASSES = 6, SORT_CLASSES = 3 * WIDTH_CLASSES;
     const uint32_t m = n - first;
-    const bool sorted = BRMI_BIN_SORT && !ALPHA && m >= BRMI_BIN_SORT_MIN && m <= BIN_ORDER_CAP;
+    const bool sorted = !ALPHA && m >= BRMI_BIN_SORT_MIN && m <= BIN_ORDER_CAP;
     if (sorted) {
         if (tid < SORT_CLASSES) classCount[tid] = 0u;
         __syncthreads();
@@ -1166,15 +1096,9 @@ __global__ void __launch_bounds__(BRMI_BIN_THREADS, ALPHA ? BRMI_BIN_ALPHA_WAVES
     auto record_at = [&](uint32_t idx) { return first + (sorted ? (uint32_t)order[idx] : idx); };
     BinRecord pending{}; uint32_t riPending = 0;
     if (cs + sub < ce) { riPending = record_at(cs + sub); pending = recs[riPending]; }
-#ifdef BRMI_TILE_STAMPS
-    wPrev = __builtin_amdgcn_s_memtime();
-#endif
     for (uint32_t base = cs; base < ce; base += per) {
         const uint32_t idx = base + sub;
         const BinRecord r = pending;
-#ifdef BRMI_TILE_STAMPS
-        { uint32_t probe_ = r.clusterIndex; asm volatile("" :: "v"(probe_)); const unsigned long long now_ = __builtin_amdgcn_s_memtime(); wWait += now_ - wPrev; wPrev = now_; }     // the record has arrived
-#endif
         if (idx + per < ce) { riPending = record_at(idx + per); pending = recs[riPending]; }
         if (idx >= ce) continue;
         const uint32_t rows = (r.triAndFlags >> 16) & 0xFFu;
@@ -1186,12 +1110,8 @@ __global__ void __launch_bounds__(BRMI_BIN_THREADS, ALPHA ? BRMI_BIN_ALPHA_WAVES
                 raster_row(sink, NoAlpha{}, py, r.minX, r.rectWidth, (r.triAndFlags & 0x100u) != 0, sb0, sb1, r.dx_b0, r.dx_b1, -(r.dx_b0 + r.dx_b1), r.d0, r.d1, r.d2, r.clusterIndex, r.triAndFlags & 0x7Fu,
                            x0, x0 + BIN_W - 1);
         }
-#ifdef BRMI_TILE_STAMPS
-        { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); wWalk += now_ - wPrev; wPrev = now_; }
-#endif
     }
     }   // row classes
-    BSTAMP(1);
     if (ALPHA) {
         // Scenes with alpha-tested materials (round 4).  A slice holds at most ALPHA_LIST records here (the plan's slices; launch_raster), in arrival order:
         // opaque and tested triangles mixed, two floor triangles that span the bin beside hundreds of 10-pixel slivers.  One look at every record's
@@ -1234,7 +1154,6 @@ __global__ void __launch_bounds__(BRMI_BIN_THREADS, ALPHA ? BRMI_BIN_ALPHA_WAVES
         if (tid == BRMI_BIN_THREADS - 1u && listed == ALPHA_LIST) { taskStart[ALPHA_LIST] = runA; rowStart[ALPHA_LIST] = (uint16_t)runO; }      // j never reaches ALPHA_LIST in the loop above
         __syncthreads();
         const uint32_t total = listed ? taskStart[listed] : 0u, totalRows = listed ? rowStart[listed] : 0u;
-        BSTAMP(2);
         // ---- rows of the opaque records
         for (;;) {
             uint32_t tb = 0;
@@ -1256,8 +1175,6 @@ __global__ void __launch_bounds__(BRMI_BIN_THREADS, ALPHA ? BRMI_BIN_ALPHA_WAVES
                                x0, x0 + BIN_W - 1);
             }
         }
-        BSTAMP(1);
-#if BRMI_ALPHA_COMPACT
         // Round 4.  A segment's lane used to test its pixels where it found them: of the 64 lanes of a wave a third had a covered pixel whose key could
         // still win at any one step, and the wave ran the sampler (texcoord -> texel addresses -> dependent fetches -> filter: the bulk of this pass,
         // which was 53 % of the kernel's wave-cycles on the San-Miguel-class frame) for them alone, eight times per task.  Now the walk only FINDS
@@ -1280,7 +1197,6 @@ __global__ void __launch_bounds__(BRMI_BIN_THREADS, ALPHA ? BRMI_BIN_ALPHA_WAVES
                 }
                 qHead += n;
                 wave_lds_sync();
-                BSTAMP(6);      // (instrumented builds: the sampling of 64 waiting pixels)
             };
             // (tasks are taken 64 at a time from a counter of the workgroup: segments cost anything from nothing to sixteen sampled pixels, and with a
             // fixed deal the waves waited 14 % of the kernel's wave-cycles for the slowest one at the barrier behind this pass)
@@ -1312,8 +1228,7 @@ __global__ void __launch_bounds__(BRMI_BIN_THREADS, ALPHA ? BRMI_BIN_ALPHA_WAVES
                     if (on) w = seg_begin(r.minX, r.rectWidth, (r.triAndFlags & 0x100u) != 0, sb0, sb1, r.dx_b0, r.dx_b1, -(r.dx_b0 + r.dx_b1), sx0, sx1);
                     dx0 = r.dx_b0; dx1 = r.dx_b1; d0 = r.d0; d1 = r.d1; d2 = r.d2; cluster = r.clusterIndex; tri = r.triAndFlags & 0x7Fu; mat = ar.materialDataIndex; at = ar.tri;
                 }
-                { uint32_t probe_ = cluster + mat; asm volatile("" :: "v"(probe_)); }
-                BSTAMP(7);      // (instrumented builds: a task's record has arrived and its segment is set up)
+                { uint32_t probe_ = cluster + mat; asm volatile("" :: "v"(probe_)); }      // (waits for the task's record here, ahead of the walk: the schedule this kernel was measured with)
 #pragma nounroll
                 for (int k = 0; k < (1 << ALPHA_SEG_SHIFT); k++) {
                     const bool act = on && w.px <= w.x1;
@@ -1325,7 +1240,7 @@ __global__ void __launch_bounds__(BRMI_BIN_THREADS, ALPHA ? BRMI_BIN_ALPHA_WAVES
                     const uint32_t cell = (uint32_t)((w.px - x0) * BIN_ROWS + (py - y0)) & 0xFFFu;
                     const bool want = act && cov && key < *(volatile const unsigned long long*)&tile[cell];
                     const unsigned long long m = __ballot(want);
-                    if (AQ < 128u && qTail - qHead + (uint32_t)__popcll(m) > AQ) { BSTAMP(3); drain(qTail - qHead); }      // (a 64-entry ring: make room first)
+                    if (AQ < 128u && qTail - qHead + (uint32_t)__popcll(m) > AQ) drain(qTail - qHead);      // (a 64-entry ring: make room first)
                     if (want) {
                         const uint32_t e = (qTail + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))) & (AQ - 1u);
                         const f2 uv = pixel_texcoord(at, w.b0, w.b1, b2);
@@ -1333,17 +1248,13 @@ __global__ void __launch_bounds__(BRMI_BIN_THREADS, ALPHA ? BRMI_BIN_ALPHA_WAVES
                     }
                     qTail += (uint32_t)__popcll(m);
                     if (act) { w.b0 += dx0; w.b1 += dx1; w.px++; }
-                    if (qTail - qHead >= 64u) { BSTAMP(3); drain(64u); }
+                    if (qTail - qHead >= 64u) drain(64u);
                 }
-                BSTAMP(3);
             }
             if (qTail != qHead) drain(qTail - qHead);
         }
-#endif
-        BSTAMP(3);
     }
     __syncthreads();
-    BSTAMP(4);
     // ---- a slice of a shared bin: park the tile; the slice that arrives last folds the others in and goes on to merge
     bool atomicMerge = false, fold = true;
     if (shared) {
@@ -1410,21 +1321,11 @@ __global__ void __launch_bounds__(BRMI_BIN_THREADS, ALPHA ? BRMI_BIN_ALPHA_WAVES
             if (m2.x != g.x || m2.y != g.y) dst[q] = m2;
         }
     }
-    BSTAMP(5);
-#ifdef BRMI_TILE_STAMPS
-    if (tid == 0 && (a.debugFlags & 0x400)) {       // timeline: one entry per work item
-        unsigned long long* w = a.debugStamps + 64u + 4u * (size_t)itemIndex;
-        w[0] = wgStart; w[1] = __builtin_amdgcn_s_memrealtime(); w[2] = (unsigned long long)(n - first) | ((unsigned long long)item << 32); w[3] = wWalk;
-    }
-#endif
     __syncthreads();                                    // the merge has read the tile (and everyone has read curItem)
     if (tid == 0) curItem = staticItems + atomicAdd(&a.binPlan[1], 1u);
     __syncthreads();
     itemIndex = curItem;
     }   // work items
-#ifdef BRMI_TILE_STAMPS
-    if ((threadIdx.x & 63u) < 8u && (a.debugFlags & 0x200)) { unsigned long long v = 0; for (int k = 0; k < 8; k++) if ((threadIdx.x & 63u) == (uint32_t)k) v = bph[k]; atomicAdd(a.debugStamps + 32u + (threadIdx.x & 63u), v); }
-#endif
 }
 
 // The plan of the k_raster_bins launch that follows (the last workgroup of k_raster_overflow): every bin's record count is taken (and cleared
@@ -1491,16 +1392,6 @@ BRMI_DEV void plan_bins(const RasterArgs& a) {
 // THREADS: 256, or 1024 for surfaces of more than 4096 bins (an 8K frame has 8,100: the plan is ONE workgroup's work and was 51 us of the Zorah-class frame's chain)
 template <bool ALPHA, uint32_t THREADS = 256>
 __global__ void __launch_bounds__(THREADS) k_raster_overflow(RasterArgs a) {
-    wave_prio<PRIO_BINS>();
-#ifdef BRMI_TILE_STAMPS
-    if (blockIdx.x == 0u) {        // (instrumented builds: how long the plan takes, in 10 ns units; slots 40 / 41 of the stamp words)
-        const unsigned long long t0_ = __builtin_amdgcn_s_memrealtime();
-        plan_bins(a);
-        __syncthreads();
-        if (threadIdx.x == 0 && (a.debugFlags & 0x400)) { atomicAdd(a.debugStamps + 40u, __builtin_amdgcn_s_memrealtime() - t0_); atomicAdd(a.debugStamps + 41u, 1ull); }
-        return;
-    }
-#endif
     if (blockIdx.x == 0u) {       // (the first workgroup: it is what the next launch waits for, so it should not queue behind the walkers)
         if (a.wideFeedback && threadIdx.x == 0u) __hip_atomic_store(a.wideFeedback, a.counters[a.wideCounter], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         plan_bins(a); return;
@@ -1553,7 +1444,6 @@ struct RetestArgs {
     uint32_t* counters; uint32_t* lateList; uint32_t* heldFeedback;      // (host-mapped word or null: the held count, for the grids of the frames that follow)
 };
 __global__ void __launch_bounds__(256) k_retest_held(RetestArgs a) {
-    wave_prio<PRIO_RASTER>();
     const uint32_t n = min(a.counters[CNT_HELD1], a.capacity);
     if (a.heldFeedback && blockIdx.x == 0u && threadIdx.x == 0u) __hip_atomic_store(a.heldFeedback, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     const brmi_view_raster_info ri = a.viewRasterInfo[0];      // (single view: ClusterSetup::viewId is the main camera's)
@@ -1614,7 +1504,7 @@ int launch_raster(brmi_pass* p, uint32_t phase, hipStream_t s) {
     a.wideFeedback = (phase == 1 && p->phase2FeedbackDev) ? p->phase2FeedbackDev + 7 : nullptr;
     const dim3 wgrid(std::max(64u, std::min(8192u, lastWide * 8u)));      // eight single-wave workgroups per queued triangle (WIDE_SHARES)
     // (the interleaved partition's surface rows are not the frame rows the boxes are in: there the second build redoes everything)
-    a.chainDirty = (BRMI_CHAIN_DIRTY_BLOCKS && phase == 2 && p->stripes.count <= 1u) ? p->wsPtr<uint8_t>(p->ws.chainDirty) : nullptr; a.chainBlocksX = (p->cfg.width + 31u) / 32u;
+    a.chainDirty = (phase == 2 && p->stripes.count <= 1u) ? p->wsPtr<uint8_t>(p->ws.chainDirty) : nullptr; a.chainBlocksX = (p->cfg.width + 31u) / 32u;
     p->chainDirtyTracked = a.chainDirty != nullptr;
     if (phase == 2) { a.firstCounter = CNT_VISIBLE; a.countCounter = CNT_VISIBLE2; }   // clusters [visible1, visible1 + visible2)
     a.vis = static_cast<unsigned long long*>(p->res[BRMI_RES_VISIBILITY]);
@@ -1624,32 +1514,29 @@ int launch_raster(brmi_pass* p, uint32_t phase, hipStream_t s) {
     a.binCapacity = p->binCapacity; a.binsX = p->binsX; a.binsY = p->binsY;
     a.overflow = p->wsPtr<BinRecord>(p->ws.binOverflow); a.overflowPerStripe = p->binOverflowPerStripe;
     a.objConst = p->wsPtr<float>(p->ws.objConst);
-    a.bigTriArea = p->bigTriArea; a.bigTriAreaAlpha = p->bigTriAreaAlpha; a.debugFlags = p->rasterDebug;
+    a.bigTriArea = p->bigTriArea; a.bigTriAreaAlpha = p->bigTriAreaAlpha;
     a.bigTriAreaDense = p->bigTriAreaDense; a.denseClusterCount = p->denseClusterCount;
     // alpha-tested scenes: a slice's alpha records all go through the task list of k_raster_bins<true> (BRMI_ALPHA_LIST entries), so no slice is longer than that
     a.binMinSlice = p->sceneHasAlphaTest ? std::min(p->binMinSlice, (uint32_t)BRMI_ALPHA_LIST) : p->binMinSlice;
     a.binSharedSlice = std::max(32u, std::min(p->binSharedSlice, a.binMinSlice) & ~31u);        // a multiple of the 32 records a step walks: no slice of the plan is empty
     a.binPlan = p->wsPtr<uint32_t>(p->ws.binPlan); a.binItems = p->wsPtr<uint32_t>(p->ws.binItems); a.binScratch = p->wsPtr<unsigned long long>(p->ws.binScratch);
     a.binScratchTiles = p->binScratchTiles; a.binItemCapacity = p->binItemCapacity;
-    // the LDS window k_raster counts its records per bin in: every bin of the surface when that is at most 2048 cells (8 KB), else 2048 (BRMI_BIN_TABLE: 256 = the round-3 window only)
-    static const uint32_t tableEnv = (uint32_t)std::max(256l, std::min(2048l, experiment("bin_table", BIN_TABLE_MAX)));
-    a.tableCells = std::max<uint32_t>(BIN_WINDOW, std::min<uint32_t>(tableEnv, (p->binsX * p->binsY + 63u) & ~63u));
+    // the LDS window k_raster counts its records per bin in: every bin of the surface when that is at most 2048 cells (8 KB), else 2048
+    a.tableCells = std::max<uint32_t>(BIN_WINDOW, std::min<uint32_t>(BIN_TABLE_MAX, (p->binsX * p->binsY + 63u) & ~63u));
     a.binAlpha = p->wsPtr<AlphaRecord>(p->ws.binAlpha); a.overflowAlpha = p->wsPtr<AlphaRecord>(p->ws.overflowAlpha);
     a.clusterUv = p->wsPtr<ClusterUv>(p->ws.clusterUv);
     a.alphaMats = p->wsPtr<AlphaMaterial>(p->ws.alphaMats);
     // (k_raster_bins<true> packs the material index of a waiting pixel with its 12-bit tile cell into one word)
     if (p->sceneHasAlphaTest && p->scene.materialCount > (1u << 20)) return fail(p, BRMI_ERR_INVALID, "brmi_raster: %u materials in a scene with alpha-tested ones (at most %u)", p->scene.materialCount, 1u << 20);
     if (p->sceneHasAlphaTest) if (int rc = ensure_frame_constants(p, s)) return rc;
-    a.debugStamps = p->wsPtr<unsigned long long>(p->ws.debugStamps);
     // the pool of k_raster_bins: four 512-thread workgroups per CU is what the LDS holds; phase 2 rarely has an item at all
     // Round 4: phase-2 launches are sized by what the host last saw phase 2 draw (the host-mapped word of the ranking kernel, read without a wait: a frame
     // or two old; every kernel here strides its grid or takes items by ticket, so any size gives the same keys).  Beside another frame's shading half a
     // wave that finds nothing still has to find a slot -- 200 VGPRs for k_raster<true>, 66 KB of LDS for a k_raster_bins<true> workgroup -- and the three
     // phase-2 launches of a still camera cost the San-Miguel-class frame ~150 us of its geometry chain in flight (kernel stats: k_raster<true> 61 us,
     // k_raster_overflow<true> 53, k_raster_bins<true> 150 per launch on average, phase 1 and 2 alike).
-    static const bool sizeByHint = experiment("phase2_sized", 1) != 0;
     uint32_t hint2 = 0xFFFFFFFFu;
-    if (phase == 2 && sizeByHint && p->phase2FeedbackHost) hint2 = *reinterpret_cast<volatile uint32_t*>(p->phase2FeedbackHost);
+    if (phase == 2 && p->phase2FeedbackHost) hint2 = *reinterpret_cast<volatile uint32_t*>(p->phase2FeedbackHost);
     auto pow2_at_least = [](uint32_t v) { uint32_t r = 1; while (r < v && r < (1u << 30)) r <<= 1; return r; };
     const bool sized2 = hint2 < 128u;
     const dim3 bgrid(phase == 2 ? (sized2 ? std::max(16u, std::min(256u, pow2_at_least(hint2 * 2u))) : std::min(p->binGrid, 256u)) : p->binGrid);
@@ -1664,14 +1551,14 @@ int launch_raster(brmi_pass* p, uint32_t phase, hipStream_t s) {
     if (direct2) a.bigTriArea = a.bigTriAreaAlpha = a.bigTriAreaDense = 0x3FFFFFFF;
     // phase 2 rarely has more than a handful of clusters: 2048 workgroups (the kernel strides; two waves per SIMD) start and retire a little
     // faster than 8192 that find nothing (-3 us per frame)
-    static const uint32_t grid2 = (uint32_t)std::max(64l, experiment("raster_grid2", 2048));
+    constexpr uint32_t grid2 = 2048;
     const dim3 rgrid(phase == 2 ? std::min(p->rasterGrid, sized2 ? std::max(128u, std::min(grid2, pow2_at_least(hint2 * 16u))) : grid2) : p->rasterGrid);
     const dim3 ogrid(phase == 2 && sized2 ? std::max(2u, std::min(129u, hint2 / 4u + 2u)) : 129u);      // (block 0 plans the bins launch; the others walk the overflow queues)
     if (p->sceneHasAlphaTest) {
         hipLaunchKernelGGL(k_raster<true>, rgrid, dim3(64), a.tableCells * 4u, s, a);
         if (!direct2 && wideOn) hipLaunchKernelGGL(k_raster_wide<true>, wgrid, dim3(64), 0, s, a);
         if (!direct2) hipLaunchKernelGGL(k_raster_overflow<true>, ogrid, dim3(256), 0, s, a);
-        if (!direct2 && !(p->rasterDebug & 4)) hipLaunchKernelGGL(k_raster_bins<true>, bgrid, dim3(BRMI_BIN_THREADS), 0, s, a);
+        if (!direct2) hipLaunchKernelGGL(k_raster_bins<true>, bgrid, dim3(BRMI_BIN_THREADS), 0, s, a);
     } else {
         // round 6: the lean form for frames of very many clusters (k_raster<false, true>), the general launch behind it for what it leaves.  Decided from what the host last
         // saw of such launches (host-mapped words 8 / 9: the main launch's cluster count, the general launch's; a frame or two old -- either way the same keys).
@@ -1704,7 +1591,7 @@ int launch_raster(brmi_pass* p, uint32_t phase, hipStream_t s) {
             if (p->binsX * p->binsY > 4096u) hipLaunchKernelGGL((k_raster_overflow<false, 1024>), dim3((ogrid.x - 1u + 3u) / 4u + 1u), dim3(1024), 0, s, a);
             else hipLaunchKernelGGL(k_raster_overflow<false>, ogrid, dim3(256), 0, s, a);
         }
-        if (!direct2 && !(p->rasterDebug & 4)) hipLaunchKernelGGL(k_raster_bins<false>, bgrid, dim3(BRMI_BIN_THREADS), 0, s, a);
+        if (!direct2) hipLaunchKernelGGL(k_raster_bins<false>, bgrid, dim3(BRMI_BIN_THREADS), 0, s, a);
     }
     BRMI_LAUNCH_CHECK(p, "k_raster");
     if (hold) {
@@ -1724,7 +1611,7 @@ int launch_raster(brmi_pass* p, uint32_t phase, hipStream_t s) {
         l.drawList = r.lateList; l.countCounter = CNT_LATE1; l.countFeedback = p->phase2FeedbackDev ? p->phase2FeedbackDev + 5 : nullptr;
         l.wideCounter = CNT_WIDE1B; l.wideFeedback = nullptr;
         // what the late pass draws changes the depth under it: it records the 32 x 32 px blocks its triangles may touch, like phase 2
-        l.chainDirty = BRMI_CHAIN_DIRTY_BLOCKS ? p->wsPtr<uint8_t>(p->ws.chainDirty) : nullptr; l.chainBlocksX = (p->cfg.width + 31u) / 32u;
+        l.chainDirty = p->wsPtr<uint8_t>(p->ws.chainDirty); l.chainBlocksX = (p->cfg.width + 31u) / 32u;
         p->chainDirtyTracked = l.chainDirty != nullptr; p->chainBuiltInRaster = true;
         // few late clusters (a still or slowly moving camera: the prediction and the re-test ask the same question of nearly the same depth): every triangle through the
         // row re-deal with global atomics, ONE launch, as the small phase 2; many: records, plan and bins once more

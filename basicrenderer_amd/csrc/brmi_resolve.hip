@@ -58,7 +58,6 @@ BRMI_DEV f3 oct_decode_normal(uint32_t packed) {
 // and the decoded vertex normals are evaluated once per triangle / vertex here with the shader's operation order; the pixel
 // pass then only evaluates the part that depends on the pixel.  (The reference shader recomputes all of it per pixel.)
 __global__ void __launch_bounds__(64) k_resolve_setup(GBufferArgs a) {
-    wave_prio<PRIO_SETUP>();
     __shared__ float cx[BRMI_MESHLET_MAX_VERTS], cy[BRMI_MESHLET_MAX_VERTS], cw[BRMI_MESHLET_MAX_VERTS];
     const uint32_t lane = threadIdx.x;
     // part 1 runs while the rasteriser and the phase-2 culling are still at work: it reads the phase-1 count only (final since the compaction)
@@ -276,9 +275,6 @@ constexpr int RESOLVE_WATERFALL = BRMI_RESOLVE_WATERFALL;     // distinct mesh i
 #ifndef BRMI_GBP_WAVES
 #define BRMI_GBP_WAVES 2
 #endif
-#ifndef FRAME_EARLY
-#define FRAME_EARLY 1
-#endif
 #ifndef BRMI_GBPM_WAVES
 #define BRMI_GBPM_WAVES 3
 #endif
@@ -452,11 +448,10 @@ BRMI_DEV void gbuffer_body(const GBufferArgs& a, const Epi& epi) {
                         const float invmax = rsqrtf_(max2(dot3(T, T), dot3(B, B)));
                         Tn = T * invmax; Bn = B * invmax;
                     };
-                    // with parallax the frame is needed before the fetches; without, building it next to its only use keeps six registers free over them.
-                    // BuildMaterialUvBindings: the frame follows the normal slot's UV set, else the height slot's
+                    // with parallax the frame is needed before the fetches.  BuildMaterialUvBindings: the frame follows the normal slot's UV set, else the height slot's
                     if (PARALLAX && (flags & (BRMI_MATERIAL_NORMAL_MAP | BRMI_MATERIAL_PARALLAX))) { use_set((flags & BRMI_MATERIAL_NORMAL_MAP) ? mat->normalUvSetIndex : mat->heightUvSetIndex); cotangent_frame(); }
                     // single-set scenes: the frame before the fetches too -- six values live over them instead of the corner positions and the barycentric derivatives (15)
-                    if (!PARALLAX && FRAME_EARLY && (flags & BRMI_MATERIAL_NORMAL_MAP)) { use_set(mat->normalUvSetIndex); cotangent_frame(); }
+                    if (!PARALLAX && (flags & BRMI_MATERIAL_NORMAL_MAP)) { use_set(mat->normalUvSetIndex); cotangent_frame(); }
                     if (PARALLAX && (flags & BRMI_MATERIAL_PARALLAX)) {       // PSO_PARALLAX (utilities.hlsli:1869-1897): every slot on the height map's UV set moves with it
                         const brmi_camera* cam = sc.cameras + sc.perFrame->mainCameraIndex;
                         const f3 camPos{cam->positionWorldSpace[0], cam->positionWorldSpace[1], cam->positionWorldSpace[2]};
@@ -499,7 +494,6 @@ BRMI_DEV void gbuffer_body(const GBufferArgs& a, const Epi& epi) {
                         }
                     }
                     if (flags & BRMI_MATERIAL_NORMAL_MAP) {
-                        if (!PARALLAX && !FRAME_EARLY) { use_set(mat->normalUvSetIndex); cotangent_frame(); }
                         f3 tn = normalize3(sNormal * 2.0f - f3{1.0f, 1.0f, 1.0f});
                         if (flags & BRMI_MATERIAL_NEGATE_NORMALS) tn = -tn;
                         if (flags & BRMI_MATERIAL_INVERT_NORMAL_GREEN) tn.y = -tn.y;
@@ -582,7 +576,6 @@ BRMI_DEV void gbuffer_body(const GBufferArgs& a, const Epi& epi) {
 }
 template <bool INLINE_TABLES, bool TEXTURED, bool PARALLAX = false, bool MULTI_UV = false, int SLIM = 0>
 __global__ void __launch_bounds__(256, INLINE_TABLES ? 1 : (MULTI_UV ? (PARALLAX ? BRMI_GBPM_WAVES : BRMI_GBM_WAVES) : (PARALLAX ? BRMI_GBP_WAVES : (TEXTURED ? BRMI_GBT_WAVES : BRMI_GB_WAVES)))) k_gbuffer(GBufferArgs a) {
-    wave_prio<PRIO_GBUFFER>();
     gbuffer_body<INLINE_TABLES, TEXTURED, PARALLAX, MULTI_UV, SLIM>(a, NoEpilogue{});
 }
 

@@ -154,9 +154,6 @@ BRMI_DEV f3 diffuse_eon(f3 albedo, float rough, float NdotV, float NdotL, float 
 //   [1] attenuation polynomial, conservative upper bound of maxRange^2
 //   [2] colour x intensity, cos(inner)        [3] spot: normalize(direction), cos(outer); any other light: 0, -2
 struct ShadeLightRecord { float r0[4], r1[4], r2[4], r3[4]; };   // the same record as plain words (scalar loads)
-#ifndef BRMI_SHADE_METAL_STASH
-#define BRMI_SHADE_METAL_STASH 1      // the stand-alone variant of k_shade<0> parks the metal lobe's inputs in LDS
-#endif
 
 struct ShadeArgs {
     ShadeTables tables;
@@ -221,13 +218,9 @@ BRMI_DEV RawPixel empty_raw_pixel() { RawPixel r{}; r.d = as_f32(BRMI_DEPTH_EMPT
 
 // what the specialised kernel keeps in flight for the next tile: coat / fuzz words reduced to the coat weight
 // `tileBase` (first pixel of the wave's tile) is wave-uniform: plane base + tile offset is scalar, the lane index is the only vector part
-#ifndef BRMI_SHADE_PREFETCH_AXIS
-#define BRMI_SHADE_PREFETCH_AXIS 1
-#endif
 BRMI_DEV RawPixel load_raw_pixel_plain(const ShadeArgs& a, uint64_t tileBase, uint32_t lane, uint32_t px, uint32_t py) {
     RawPixel r;
-    if (BRMI_SHADE_PREFETCH_AXIS) { r.ax = a.tables.x[px]; r.ay = a.tables.y[py]; }
-    else { r.ax.tile = px; r.ay.tile = py; }
+    r.ax = a.tables.x[px]; r.ay = a.tables.y[py];
     // read once: streaming loads
     const float* dp = a.depth + tileBase; const float4* np = a.normals + tileBase; const uint32_t* ap = a.albedo + tileBase; const uint32_t* mp = a.metallicRoughness + tileBase;
     const unsigned long long* ep = a.emissive + tileBase; const uint16_t* cp = reinterpret_cast<const uint16_t*>(a.coat + tileBase);
@@ -311,9 +304,6 @@ BRMI_DEV f3 fma3v(f3 a, f3 s, f3 b) { return f3{__builtin_fmaf(a.x, s.x, b.x), _
 // every term of the sum.  A tile takes this path when ALL its live pixels are that rough (wave-uniform branch); smoother tiles keep the exact forms.
 // What stays exact on both paths: N and V (the bent normal cancels to ~1e-4 where the stored normal faces away, and N.V, N.L scale terms that vanish with them),
 // and L wherever |N.L| < SHADE_FAST_MIN_NOL.  Fast: L elsewhere, H, and the dot products N.H, L.H, V.L -- two normalisations and three dot products per light evaluation.
-#ifndef BRMI_SHADE_FAST_DIRECTIONS
-#define BRMI_SHADE_FAST_DIRECTIONS 1
-#endif
 struct FastDirections { static constexpr bool value = true; };
 struct ExactDirections { static constexpr bool value = false; };
 constexpr float SHADE_FAST_ALPHA = 0.1f, SHADE_FAST_MIN_NOL = 4.0e-3f;
@@ -427,8 +417,7 @@ BRMI_DEV uint32_t shade_pixel(const ShadeArgs& a, const ShadeFrame& k, const flo
                 invProj.m[r][0] = p4.x; invProj.m[r][1] = p4.y; invProj.m[r][2] = p4.z; invProj.m[r][3] = p4.w;
                 viewInv.m[r][0] = v4.x; viewInv.m[r][1] = v4.y; viewInv.m[r][2] = v4.z; viewInv.m[r][3] = v4.w;
             }
-            AxisEntry ax = raw.ax, ay = raw.ay;
-            if (MODE == 0 && !BRMI_SHADE_PREFETCH_AXIS) { ax = a.tables.x[raw.ax.tile]; ay = a.tables.y[raw.ay.tile]; }
+            const AxisEntry ax = raw.ax, ay = raw.ay;
             float uvx = ax.uv, uvy = ay.uv;
             uvy = 1.0f - uvy;
             const f4 clipPos{uvx * 2.0f - 1.0f, uvy * 2.0f - 1.0f, 1.0f, 1.0f};
@@ -453,7 +442,7 @@ BRMI_DEV uint32_t shade_pixel(const ShadeArgs& a, const ShadeFrame& k, const flo
     uint32_t uci = 0u, listBase = 0u, listCount = 0u;
     // every live pixel of the tile at least SHADE_FAST_ALPHA rough (plain pixels only: a coat has a roughness of its own): the tile's direction vectors take the fast forms
     bool fastTile = false;
-    if (MODE == 0 && BRMI_SHADE_FAST_DIRECTIONS) {
+    if (MODE == 0) {
         const float prq = clampf(unorm8[(mr >> 8) & 0xFFu], BRMI_MIN_PERCEPTUAL_ROUGHNESS, 1.0f);
         fastTile = !__any(live && prq * prq < SHADE_FAST_ALPHA);
     }
@@ -477,11 +466,7 @@ BRMI_DEV uint32_t shade_pixel(const ShadeArgs& a, const ShadeFrame& k, const flo
         f.NdotV = max2(BRMI_MIN_N_DOT_V, NdotVraw);
         uint32_t opIndex = (uint32_t)(ns.w + 0.5f);
         if (opIndex >= a.openpbrMaterialCount) opIndex = 0;
-#ifdef BRMI_ABLATE_MATCONST
-        const MatConst mc = a.matConst[0];      // (experiment: one wave-uniform record instead of a gather per pixel; wrong image for mixed scenes)
-#else
         const MatConst mc = a.matConst[opIndex];
-#endif
         const float baseWeight = mc.baseWeight, specularWeight = mc.specularWeight;
         const f3 specularColor{mc.specR, mc.specG, mc.specB};
         const f3 weightedBaseColor = satq3(baseColor * baseWeight);
@@ -537,11 +522,7 @@ BRMI_DEV uint32_t shade_pixel(const ShadeArgs& a, const ShadeFrame& k, const flo
         const bool mine = (same >> lane_id()) & 1ull;
         // The records of a cluster's lights lie in list order (k_lc_fill), so light q of the list is ONE wave-uniform 64 B record: a scalar
         // load brings it into SGPRs -- no staging registers (16 VGPRs) and no v_readlane per field.
-#ifdef BRMI_ABLATE_LIGHTREC
-        const float4* recBase = a.shadeLights;      // (experiment: every tile reads the head of ONE table -- scalar-cache hits; wrong image)
-#else
         const float4* recBase = a.clustered ? a.listRecords + (size_t)listBase * 4u : a.shadeLights;
-#endif
         // (two instantiations of the loop, chosen per tile: FAST = the direction vectors within an ulp, see SHADE_FAST_ALPHA)
         auto light_loop = [&](auto fastTag) {
             constexpr bool FAST = decltype(fastTag)::value;

@@ -248,9 +248,6 @@ BRMI_DEV void build_shade_rows(const Luts& L, float ior, float alpha, ShadeRows&
 // one sample of a folded row at cos(theta) (any finite value: saturated here)
 BRMI_DEV float sample_folded_row(const float2* row, float cosT) {
     BRMI_FP_FAST
-#ifdef BRMI_ABLATE_ROWS
-    return cosT * 0.5f;      // (experiment: the table gathers gone; wrong image)
-#endif
     const float x = satq(cosT) * TBL_M1;
     const float x0f = floorf(x);
     const float2 p = row[(uint32_t)x0f];

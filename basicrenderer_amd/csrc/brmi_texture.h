@@ -283,36 +283,7 @@ BRMI_DEV AlphaMaterial load_alpha_material(MatPtr m, TexPtr textures, uint32_t t
     return r;
 }
 // one level of one texture: `flags` are the texture's six bits
-// (measured at compile time, round 4: with this path beside the general one the rasteriser's alpha kernels need ~40 more registers and spill; off)
-#ifndef BRMI_ALPHA_POW2_PATH
-#define BRMI_ALPHA_POW2_PATH 0
-#endif
-// the bilinear footprint of a power-of-two level without a branch (the addressing of sample_prepared_pow2, its per-axis constants derived per lane:
-// the lanes of the rasteriser's pixel loops belong to different materials)
-BRMI_DEV float alpha_level_pow2(const float* unorm, const uint32_t* base, uint32_t wh, uint32_t flags, f2 uv) {
-    const int wm1 = (int)(wh & 0xFFFFu), hm1 = (int)(wh >> 16);
-    const uint32_t w = (uint32_t)wm1 + 1u;
-    const float fx = uv.x * (float)(wm1 + 1) - 0.5f, fy = uv.y * (float)(hm1 + 1) - 0.5f;
-    const float tx_ = fx - floorf(fx), ty_ = fy - floorf(fy);
-    const int x0 = floor_to_int(fx), y0 = floor_to_int(fy);
-    const uint32_t modeU = (flags >> ALPHA_FLAG_ADDR_U_SHIFT) & 3u, modeV = (flags >> ALPHA_FLAG_ADDR_V_SHIFT) & 3u;
-    const int m2x = 2 * wm1 + 1, m2y = 2 * hm1 + 1;
-    const int hx = modeU == BRMI_ADDRESS_MIRROR ? m2x : wm1, ox = modeU == BRMI_ADDRESS_MIRROR ? m2x : 0x7FFFFFFF, mx = modeU == BRMI_ADDRESS_CLAMP ? -1 : hx;
-    const int hy = modeV == BRMI_ADDRESS_MIRROR ? m2y : hm1, oy = modeV == BRMI_ADDRESS_MIRROR ? m2y : 0x7FFFFFFF, my = modeV == BRMI_ADDRESS_CLAMP ? -1 : hy;
-    const uint32_t xa = (uint32_t)address_pow2(x0, mx, hx, ox), xb = (uint32_t)address_pow2(inc_sat(x0), mx, hx, ox);
-    const uint32_t ya = (uint32_t)address_pow2(y0, my, hy, oy), yb = (uint32_t)address_pow2(inc_sat(y0), my, hy, oy);
-    const uint32_t rowA = __umul24(ya, w), rowB = __umul24(yb, w);
-    const __attribute__((address_space(1))) char* g = (const __attribute__((address_space(1))) char*)base;
-    auto texel = [&](uint32_t index) { return *(GlobalTexels)(g + (uint32_t)(index << 2)); };
-    const uint32_t c00 = texel(rowA + xa), c10 = texel(rowA + xb), c01 = texel(rowB + xa), c11 = texel(rowB + xb);
-    const float a00 = unorm[c00 >> 24], a10 = unorm[c10 >> 24], a01 = unorm[c01 >> 24], a11 = unorm[c11 >> 24];
-    const float top = a00 + tx_ * (a10 - a00), bot = a01 + tx_ * (a11 - a01);
-    return top + ty_ * (bot - top);
-}
 BRMI_DEV float alpha_level(const float* unorm, const uint32_t* base, uint32_t wh, uint32_t flags, f2 uv) {
-#if BRMI_ALPHA_POW2_PATH
-    if ((flags & (ALPHA_FLAG_POW2 | ALPHA_FLAG_POINT)) == ALPHA_FLAG_POW2) return alpha_level_pow2(unorm, base, wh, flags, uv);      // (per lane; the general path below is skipped when no lane needs it)
-#endif
     const int w = (int)(wh & 0xFFFFu) + 1, h = (int)(wh >> 16) + 1;
     const uint32_t addressU = (flags >> ALPHA_FLAG_ADDR_U_SHIFT) & 3u, addressV = (flags >> ALPHA_FLAG_ADDR_V_SHIFT) & 3u;
     GlobalTexels g = as_global(base);

@@ -287,7 +287,8 @@ int brmi_debug_read_lean_queue(brmi_pass* pass, uint32_t stripe, uint32_t* runs,
  * (`held`, up to heldCapacity entries; *heldCount = how many there were) and of those the late pass drew (`late`).  held minus late was never rasterised. */
 int brmi_debug_read_held(brmi_pass* pass, uint32_t* held, uint32_t heldCapacity, uint32_t* heldCount, uint32_t* late, uint32_t lateCapacity, uint32_t* lateCount);
 
-/* Experiments only: the first `bytes` of the raster bin-record region of the workspace (instrumented builds park per-workgroup time stamps there). */
+/* Diagnostics: the first `bytes` of the raster bin-record region of the workspace; with bit 62 of `bytes` set, those bytes are zeroed instead (a following
+ * frame's records can then be told from older ones).  Waits for the device. */
 int brmi_debug_read_bin_records(brmi_pass* pass, void* dst, uint64_t bytes);
 
 /* The shading pass's in-range forms of 1 / a, sqrt(a) and 1 / sqrt(a) (brmi_device.h: the IEEE expansions without their scaling prologue and
