@@ -99,3 +99,73 @@ def test_plain_bench_times_its_steps_once_and_dumps_the_same_outputs_twice(tmp_p
         dumps.append(arrays)
     for n in dumps[0]:
         assert np.array_equal(dumps[0][n], dumps[1][n], equal_nan=True), n
+
+
+def _ring_frame_of_last_step(passes, warmup, steps):
+    """Index, in the chain of frames each one tested phase 1 against, of the frame bench.measure dumps (its last timed step): the passes of the ring render
+    frames in turn and pass k reads the chain of pass k - 1; the warm-up and the timed region each start at pass 0, so the first timed frame reads the
+    chain of the warm-up's frame on the ring's last pass, not of the warm-up's last frame.  A pass whose source has rendered nothing yet tests nothing
+    (frame 0 of the chain)."""
+    last = [-1] * passes
+
+    def frame(k):
+        last[k] = last[(k - 1) % passes] + 1
+
+    for f in range(warmup):
+        frame(f % passes)
+    for s in range(steps):
+        frame(s % passes)
+    return last[(steps - 1) % passes]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("workload", ["bistro", "san_miguel", "zorah"])
+def test_bench_dumped_frame_matches_the_oracle(workload, tmp_path):
+    """The frame the bench times, from the bench process itself: `bench.py --gpus 1 --workload W --steps 20 --warmup 5 --dump-outputs` (three passes in a ring,
+    the geometry stream and the shading streams, no host wait between frames, default tuning: the draw list, the lean rasteriser, the direct walks and the wide
+    pass decided from feedback words a frame or two old) against the oracle's frame at the same place of the chain.  The headline scene, the alpha-tested
+    San-Miguel-class frame and the Zorah-class 8K frame (lean rasteriser, half of its clusters held back).  At the dumped pixels: both visibility words and
+    depth exact, HDR within one fp16 ULP where the oracle drew something; the visible-cluster counts of both phases and the meshlets tested exact."""
+    import subprocess
+    import sys
+    import numpy as np
+    import bench
+    import orc
+    from basicrenderer_amd import Scene, compose
+    steps, warmup = 20, 5
+    d = tmp_path / workload
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", workload, "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(d)]
+    done = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+    text = done.stdout.decode(errors="replace")
+    assert done.returncode == 0, text[-4000:]
+    got = {n: np.load(d / (n + ".npy")) for n in ("hdr", "depth", "visibility", "counters")}
+
+    preset, kw, features = bench.WORKLOADS[workload]
+    W, H = bench.FRAME_SIZE.get(workload) or compose.frame_size(1, "stripes")
+    sc = Scene(preset, W, H, point_lights=bench.LIGHTS[workload], directional=True, material_features=features, **kw)
+    o = orc.OracleFrame(sc)
+    # A still camera: a frame is a function of the chain it tests phase 1 against, so the chain stops changing once it returns what it was given
+    last = _ring_frame_of_last_step(3, warmup, steps)
+    hz = None
+    for k in range(last + 1):
+        given = hz
+        hz = o.run_occlusion(given)
+        if given is not None and np.array_equal(hz[0], given[0]):
+            break
+    o.gbuffer(); o.light_cluster(); o.shade()
+    print(f"[bench dump] {workload}: the oracle's chain settled at frame {k} of {last}; visible clusters {o.count1} + {o.count2}")
+
+    px = np.sort(np.random.default_rng(0).choice(H * W, size=min(H * W, bench.DUMP_PIXELS), replace=False))
+    vis = o.vis.reshape(-1)[px]
+    assert got["visibility"].shape == (len(px), 2)
+    hi, lo = got["visibility"][:, 0].astype(np.uint64), got["visibility"][:, 1].astype(np.uint64)
+    assert np.array_equal(hi, vis >> np.uint64(32)) and np.array_equal(lo, vis & np.uint64(0xFFFFFFFF)), \
+        f"{int(((hi << np.uint64(32)) | lo != vis).sum())} of {len(px)} sampled keys differ from the oracle's"
+    assert np.array_equal(got["depth"].astype(np.float32).view(np.uint32), o.depth.reshape(-1)[px].view(np.uint32)), "linear depth"
+    covered = vis != np.uint64(0xFFFFFFFFFFFFFFFF)
+    assert covered.any()
+    a = got["hdr"].astype(np.float16).view(np.uint16).astype(np.int32)[covered]
+    b = o.hdr.reshape(-1)[px].view(np.uint16).reshape(-1, 4).astype(np.int32)[covered]
+    assert np.abs(a - b).max() <= 1, f"HDR differs by up to {int(np.abs(a - b).max())} fp16 ULP"
+    want = [o.count1, o.count2, o.counters.meshletsTested + o.counters2.meshletsTested]
+    assert got["counters"].astype(np.int64).tolist() == want, (got["counters"].tolist(), want)

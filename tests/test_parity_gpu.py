@@ -1891,3 +1891,269 @@ def test_seeded_sweep_whole_frame(case):
     b = o.hdr.view(np.uint16).reshape(H, W, 4)[covered]
     assert _half_ulp_distance(a, b).max() <= 1
     r.close()
+
+
+# ---- the bench's own arrangement against the oracle -------------------------------------------------------------------
+# Round 6's switches (the draw list, the lean rasteriser, the wide pass, the direct phase-2 and late walks, inline resolve) are decided by the host from
+# host-mapped feedback words read without a wait, a frame or two old; whatever they read, the frame must be the oracle's.
+_PLANES = ("VISIBILITY", "LINEAR_DEPTH", "HDR_COLOR", "VISIBLE_CLUSTERS", "GBUF_NORMALS", "GBUF_ALBEDO", "GBUF_COAT", "GBUF_EMISSIVE", "GBUF_FUZZ",
+           "GBUF_METALLIC_ROUGHNESS", "GBUF_MOTION_VECTORS")
+
+
+def _capture(p):
+    """Copies of the pass's outputs, made on the current stream (the one the frame ends on: ordered after it, no host wait)."""
+    from basicrenderer_amd import capi
+    return {k: p.res[capi.RES[k]].clone() for k in _PLANES}
+
+
+class _OracleRun:
+    """The oracle driven frame by frame, each frame testing phase 1 against the chain of the frame before.  A frame is a function of its camera and the
+    chain it is given, so a frame whose camera and incoming chain are the previous frame's IS that frame: it is not computed again (still cameras)."""
+
+    def __init__(self, sc):
+        import orc
+        self.sc, self.o = sc, orc.OracleFrame(sc)
+        self.hz = self.given = self.cam = None
+        self.done = self.shaded = False
+
+    def frame(self, cam=None, shade=True):
+        """cam: (cameras, cullingCameras) bytes of Scene.camera_at, or None for the scene's own camera.  Returns the OracleFrame holding the frame."""
+        key = None if cam is None else (cam[0].tobytes(), cam[1].tobytes())
+        same = self.done and key == self.cam and self.given is not None and np.array_equal(self.hz[0], self.given[0])
+        if not same:
+            if cam is not None:
+                self.sc.arrays["cameras"][:] = cam[0]; self.sc.arrays["cullingCameras"][:] = cam[1]
+            self.given, self.cam = self.hz, key
+            self.hz = self.o.run_occlusion(self.given)
+            self.done, self.shaded = True, False
+        if shade and not self.shaded:
+            self.o.gbuffer(); self.o.light_cluster(); self.o.shade()
+            self.shaded = True
+        return self.o
+
+
+def _assert_frame_is_the_oracles(got, o, what, counts=None, report=False):
+    """A captured frame (_capture) against the oracle's: visible-cluster list (both phases), keys, linear depth and the seven G-buffer planes exact, HDR within
+    one fp16 ULP where the oracle drew something.  counts: the pass's (phase-1, phase-2) visible clusters when they are this frame's."""
+    from basicrenderer_amd.renderer import detile
+    W, H = o.W, o.H
+
+    def img(k, dtype, comps=1):
+        a = got[k].cpu().numpy().view(dtype)
+        n = a.size // comps
+        return detile(a.reshape((n, comps)) if comps > 1 else a.reshape((n,)), W, H)
+
+    if counts is not None:
+        assert tuple(counts) == (o.count1, o.count2), f"{what}: visible clusters {tuple(counts)}, the oracle's {(o.count1, o.count2)}"
+    clusters = got["VISIBLE_CLUSTERS"][: o.count * 16].cpu().numpy().view(np.uint32).reshape(-1, 4)
+    assert np.array_equal(clusters, o.clusters[: o.count]), f"{what}: visible-cluster list"
+    vis = img("VISIBILITY", np.uint64)
+    assert np.array_equal(vis, o.vis), f"{what}: {int((vis != o.vis).sum())} visibility keys differ"
+    assert np.array_equal(img("LINEAR_DEPTH", np.float32).view(np.uint32), o.depth.view(np.uint32)), f"{what}: linear depth"
+    covered = o.vis != np.uint64(0xFFFFFFFFFFFFFFFF)
+    assert np.array_equal(img("GBUF_NORMALS", np.float32, 4).view(np.uint32)[covered], o.normals.view(np.uint32)[covered]), f"{what}: normals"
+    for k, dtype, ref in (("GBUF_ALBEDO", np.uint32, o.albedo), ("GBUF_METALLIC_ROUGHNESS", np.uint32, o.mr), ("GBUF_MOTION_VECTORS", np.uint32, o.motion),
+                          ("GBUF_COAT", np.uint64, o.coat), ("GBUF_EMISSIVE", np.uint64, o.emissive), ("GBUF_FUZZ", np.uint64, o.fuzz)):
+        assert np.array_equal(img(k, dtype)[covered], ref[covered]), f"{what}: {k}"
+    a = img("HDR_COLOR", np.uint64).view(np.uint16).reshape(H, W, 4)[covered].astype(np.int32)
+    b = o.hdr.view(np.uint16).reshape(H, W, 4)[covered].astype(np.int32)
+    assert np.abs(a - b).max(initial=0) <= 1, f"{what}: HDR differs by up to {int(np.abs(a - b).max())} fp16 ULP"
+    if report:
+        _report_hdr_difference(what, a, b)
+
+
+def _bench_ring(sc, n, **kw):
+    """bench.measure's arrangement: n passes with 2-phase occlusion culling in a ring (each tests phase 1 against the chain of the pass that rendered the
+    frame before), one geometry stream at priority -1 for all of them, a shading stream per pass."""
+    import torch
+    from basicrenderer_amd.renderer import VisibilityRenderer
+    passes = [VisibilityRenderer(sc, stats=k == 0, occlusion=True, band=(0, sc.height), **kw) for k in range(n)]
+    if n > 1:
+        for k in range(n):
+            passes[k].set_history_source(passes[(k - 1) % n])
+    return passes, torch.cuda.Stream(priority=-1), [torch.cuda.Stream() for _ in range(n)]
+
+
+def _switch_state(p):
+    """(held, late, lean on, clusters left to the general launch, wide-pass triangles) of the pass's last frame."""
+    c = p.counters()
+    on, general, _, _ = p.lean_clusters()
+    return dict(held=int(c.reserved[1]), late=int(c.reserved[3]), lean=on, general=general, wide=p.wide_triangles())
+
+
+BENCH_LEGS = ["bistro", "sponza", "san_miguel", "bistro_dense", "bistro_skinned", "zorah"]
+
+
+@pytest.mark.parametrize("leg", BENCH_LEGS)
+def test_bench_steady_state_against_the_oracle(leg):
+    """Every workload of bench.py (its own definitions) in the bench's arrangement with default tuning: the ring of three passes, the geometry and the shading
+    streams, update + execute per frame.  Still camera: five warm-up frames and a synchronisation (bench.measure's), then six frames without a host wait,
+    each of the last three (one per pass) copied on the stream it ends on and held against the oracle.  Then the camera path on the same ring without a wait:
+    four frames of bench.PATH_STEP and two of the fast step, as bench.camera_path sets them, every one against the oracle's frame with the same cameras.
+    The switch states of the still frames are asserted, so that the test cannot pass by leaving the adaptive paths idle."""
+    import torch
+    import bench
+    from basicrenderer_amd import Scene, compose
+    preset, kw, features = bench.WORKLOADS[leg]
+    W, H = bench.FRAME_SIZE.get(leg) or compose.frame_size(1, "stripes")
+    sc = Scene(preset, W, H, point_lights=bench.LIGHTS[leg], directional=True, material_features=features, **kw)
+    passes, geometry, shading = _bench_ring(sc, 3)
+    frame_no, copying = [0], set()
+
+    def step(cam_dev=None, cam=None):
+        k = frame_no[0] % len(passes)
+        p = passes[k]
+        if k in copying:      # (the pass's next frame rewrites what the copies read: the geometry stream waits for them, as it waits for the pass's shading anyway)
+            geometry.wait_stream(shading[k])
+            copying.discard(k)
+        with torch.cuda.stream(geometry):
+            if cam_dev is None:
+                p.update()
+            else:
+                p.set_camera_device(cam_dev[0], cam_dev[1], cam[0])
+            p.execute(shading[k])
+        frame_no[0] += 1
+        return p, k
+
+    torch.cuda.synchronize()
+    for _ in range(5):
+        step()
+    torch.cuda.synchronize()
+    got = []
+    for s in range(6):
+        p, k = step()
+        if s >= 3:
+            with torch.cuda.stream(shading[k]):
+                got.append((frame_no[0] - 1, k, _capture(p)))
+    torch.cuda.synchronize()
+    states = [_switch_state(p) for p in passes]
+    print(f"[switches] {leg} {W}x{H}: " + "; ".join(f"pass {k}: held {s['held']}, late {s['late']}, lean {s['lean']}, general {s['general']}, wide {s['wide']}"
+                                                    for k, s in enumerate(states)))
+    counts = [(c.visibleClusters, c.visibleClustersPhase2) for c in (p.counters() for p in passes)]
+    ref = _OracleRun(sc)
+    f = 0
+    for frame, k, cap in got:
+        while f < frame:
+            ref.frame(shade=False)
+            f += 1
+        o = ref.frame()
+        f += 1
+        _assert_frame_is_the_oracles(cap, o, f"{leg} still frame {frame} (pass {k})", counts=counts[k], report=True)
+    del got
+
+    if leg == "bistro":      # the headline scene: 10 k clusters, below hold_min_clusters, but phase 2 of a still camera is empty (hold_still_max)
+        assert all(s["held"] > 0 for s in states), states
+    if leg == "zorah":
+        # ~487 k clusters: the draw list and the lean rasteriser.  Nothing is left to the general launch: the Zorah-class generator builds no skinned mesh
+        # (it does not read skinned_fraction), and no triangle of the still frame overflows the lean queue
+        assert all(s["held"] > 0 and s["lean"] == 1 and s["general"] == 0 for s in states), states
+    if leg == "bistro_dense":      # ~22 k clusters: below lean_min_clusters
+        assert all(s["lean"] == 0 for s in states), states
+
+    try:
+        sc.camera_at(0.0)
+    except RuntimeError:
+        return      # (a preset without a camera path)
+    cams = [sc.camera_at(bench.PATH_STEP * (j + 1), bench.PATH_STEP * j) for j in range(4)] + [sc.camera_at(0.1 * (j + 1), 0.1 * j) for j in range(2)]
+    dev = torch.device("cuda:0")
+    cam_dev = [(torch.from_numpy(c).to(dev), torch.from_numpy(cc).to(dev)) for c, cc in cams]
+    torch.cuda.synchronize()
+    got = []
+    for j in range(len(cams)):
+        p, k = step(cam_dev[j], cams[j])
+        with torch.cuda.stream(shading[k]):
+            got.append((k, _capture(p)))
+        copying.add(k)
+    torch.cuda.synchronize()
+    counts = [(c.visibleClusters, c.visibleClustersPhase2) for c in (p.counters() for p in passes)]
+    phase2 = 0
+    for j, (k, cap) in enumerate(got):
+        o = ref.frame(cams[j])
+        phase2 += o.count2
+        _assert_frame_is_the_oracles(cap, o, f"{leg} moving frame {j} (pass {k})", counts=counts[k] if j >= len(cams) - len(passes) else None, report=True)
+        got[j] = None
+    for p in passes:
+        p.close()
+    assert phase2 > 0 or leg == "sponza", "the moving camera never gave phase 2 work"
+
+
+_SWITCH_PRESETS = [("sponza", dict()), ("bistro", dict()), ("san_miguel", dict(material_features=24)), ("bistro", dict(skinned_fraction=0.3)), ("bistro", dict(lod_builder="own"))]
+
+
+def _switch_case(seed):
+    """Case `seed` of the switch sweep, drawn from random.Random(seed): (preset, Scene kwargs, W, H, passes in flight, camera positions along the preset's path
+    (frame k sees position[k], its culling camera position[k - 1]), tuning as a function of the oracle's frame-1 visible-cluster count)."""
+    import random
+    import bench
+    rnd = random.Random(seed)
+    preset, kw = _SWITCH_PRESETS[seed % len(_SWITCH_PRESETS)]
+    W, H = rnd.randrange(960, 1921) | 1, rnd.randrange(540, 1081) | 1
+    n = rnd.randint(1, 3)
+    frames = rnd.randint(6, 8)
+    pos = [rnd.choice([0.0, 0.25, 1.0])]
+    back = rnd.randrange(3, frames)
+    steps = [rnd.choice([0.0, 0.0, bench.PATH_STEP, 0.1]) for _ in range(frames)]
+    if not any(steps[1:back]):
+        steps[rnd.randrange(1, back)] = rnd.choice([bench.PATH_STEP, 0.1])
+    for k in range(1, frames):
+        # a jump back to where the run started: last frames' chains, lists and queues are of another view
+        pos.append(pos[0] if k == back else pos[-1] + steps[k])
+    # the count thresholds around the frame's own visible count, so that the decisions flip inside the run; the edge values among them for one key at
+    # most: hold_floor 0 or 1 (the still-camera rule then decides by phase 2 alone), lean_min_clusters 1 (lean from the pass's second frame on, where it can
+    # run).  (0 for hold_min_clusters / lean_min_clusters pins a switch: drawn beside thresholds above the frame's count, nothing could change.)
+    alpha = kw.get("material_features", 0) & 16
+    edges = rnd.choice(["hold_floor", None] + ([] if alpha else ["lean_min_clusters"]))
+    counts = {k: (rnd.choice([0, 1]) if k == edges == "hold_floor" else 1 if k == edges else rnd.uniform(0.6, 1.4)) for k in ("hold_min_clusters", "lean_min_clusters", "hold_floor")}
+    fixed = dict(hold_still_max=rnd.choice([0, 1, 8, 64, 1 << 20]), hold_max_texels=rnd.choice([1, 2, 4, 8, 16]), retest_max_texels=rnd.choice([2, 4, 8, 16]),
+                 late_direct_max=rnd.choice([0, 1, 128, 1 << 30]), phase2_direct_max=rnd.choice([0, 1, 128, 1 << 30]), lean_max_general_pct=rnd.choice([0, 1, 40, 100]),
+                 lean_queue=rnd.choice([64, 4096, 1 << 20]), lean_wide_entries=rnd.choice([1, 2, 16]), wide_min_triangles=rnd.choice([0, 1, 4, 1 << 30]),
+                 wide_entries=rnd.choice([1, 16, 128]), resolve_inline=rnd.choice([-1, 0, 1]))
+
+    def tuning(visible):
+        t = {k: (v if isinstance(v, int) else max(2, int(round(visible * v)))) for k, v in counts.items()}
+        t.update(fixed)
+        return t
+
+    return preset, kw, W, H, n, pos, tuning
+
+
+@pytest.mark.parametrize("case", range(16))
+def test_adaptive_switch_sweep(case):
+    """The round-6 switches with their thresholds drawn at random (fixed seeds): the count thresholds at 0.6 - 1.4 x the frame's visible clusters, so that the
+    draw list and the lean rasteriser turn on and off from frame to frame as the camera stands, moves slowly, moves fast and jumps back -- where stale feedback,
+    the lean back-off (leanRetryIn) and last frame's queues and lists could leak into this frame -- through 1 - 3 passes in a ring.  A host synchronisation
+    after every frame (reproducible decisions; frames without one are test_bench_steady_state_against_the_oracle's), every frame against the oracle, and the
+    case must have changed the state of one of the two switches between two of its frames after the first."""
+    import torch
+    from conftest import Scene
+    preset, kw, W, H, n, pos, tuning = _switch_case(case)
+    sc = Scene(preset, W, H, point_lights=16, directional=True, **kw)
+    cams = [sc.camera_at(pos[k], pos[max(k - 1, 0)]) for k in range(len(pos))]
+    probe = _OracleRun(sc)
+    probe.frame(cams[0], shade=False)
+    o1 = probe.frame(cams[1], shade=False)
+    tun = tuning(o1.count1 + o1.count2)
+    del probe
+    desc = f"case {case}: {preset} {kw} {W}x{H}, {n} pass(es), positions {pos}, BRMI_TUNING=" + ",".join(f"{k}={v}" for k, v in tun.items())
+    print(desc)
+    with _Env(**tun):
+        passes, geometry, shading = _bench_ring(sc, n)
+    ref = _OracleRun(sc)
+    dev = torch.device("cuda:0")
+    states = []
+    for k, cam in enumerate(cams):
+        i = k % n
+        p = passes[i]
+        with torch.cuda.stream(geometry):
+            p.set_camera_device(torch.from_numpy(cam[0]).to(dev), torch.from_numpy(cam[1]).to(dev), cam[0], frame_index=k)
+            p.execute(shading[i])
+        torch.cuda.synchronize()
+        c = p.counters()
+        assert c.droppedRecords == 0 and c.droppedClusters == 0, desc
+        states.append(_switch_state(p))
+        _assert_frame_is_the_oracles(_capture(p), ref.frame(cam), f"{desc}; frame {k} (pass {i})", counts=(c.visibleClusters, c.visibleClustersPhase2))
+    for p in passes:
+        p.close()
+    print(f"[sweep] case {case}: held " + " ".join(str(s["held"]) for s in states) + " | lean " + " ".join(str(s["lean"]) for s in states))
+    hold, lean = [s["held"] > 0 for s in states[1:]], [s["lean"] for s in states[1:]]
+    assert len(set(hold)) > 1 or len(set(lean)) > 1, f"{desc}: neither the draw list nor the lean rasteriser changed state (held {[s['held'] for s in states]}, lean {lean})"
