@@ -1555,3 +1555,162 @@ def test_kernels_of_the_benchmarked_frames_use_no_scratch_memory():
         assert k in rows, (k, sorted(rows)[:80])
         assert rows[k]["vspill"] == 0 and rows[k]["scratch"] == 0, (k, rows[k])
     assert rows["k_cull_clusters<0>"]["vspill"] == 0
+
+
+# ---- the visibility buffer against an independent float64 rasteriser (tests/raster64.py) ----------------------------
+def _oracle_visibility(sc, split=None):
+    import orc
+    f = orc.OracleFrame(sc)
+    f.cull()
+    for band in ([(0, 0)] if split is None else [(0, split), (split, sc.height)]):
+        f.raster(band=band)
+    f.depth_copy()
+    return f
+
+
+def _family(name):
+    return name.split()[0]
+
+
+@pytest.fixture(scope="module")
+def adversarial():
+    import raster64
+    sc, names, intended = raster64.adversarial_scene()
+    f = _oracle_visibility(sc)
+    return sc, names, intended, f, raster64.Raster64(sc, f.clusters[: f.count])
+
+
+def test_adversarial_scene_draws_the_triangles_it_was_built_from(adversarial):
+    """From the restatement's own decode of the pages: every mesh of the scene is one listed cluster per instance holding exactly the triangles
+    the builder was given (no LOD level, weld or degenerate filter took the construction away), the families that must not draw do not, and every
+    family has decided inside pixels and decided outside pixels in its rectangles.  The caps on 'undecided' are checked from the float64 side
+    alone: 15 % of the inside pairs, 15 % of the covered pixels."""
+    import raster64
+    sc, names, intended, f, r = adversarial
+    assert (r.scissor == [0, 0, sc.width, sc.height]).all() and (sc.width % 8, sc.height % 8) != (0, 0)
+    for m, tris in intended.items():
+        got = r.triangle_positions(m)
+        instances = int((r.mesh_index == m).sum())
+        assert instances == (2 if _family(names[m]) in ("1", "2", "5") else 1), names[m]
+        assert sorted(t.tobytes() for t in got) == sorted([t.tobytes() for t in tris] * instances), names[m]
+    raster64.caps_hold(r, 0.15, "adversarial scene")
+    per_family = {}
+    for name, (inside, outside) in r.family_coverage(names).items():
+        a, b = per_family.get(_family(name), (0, 0))
+        per_family[_family(name)] = (a + inside, b + outside)
+    print("[raster64] decided (inside, outside) pairs per family:", per_family)
+    assert sorted(per_family) == sorted(["1", "2", "3", "4", "5", "6", "7", "8", "10", "11"]) and all(a > 0 and b > 0 for a, b in per_family.values()), per_family
+    # ... and so has every mesh on its own (the fan, the strip and the wedges of family 2 each), but the two that must draw nothing
+    per_mesh = r.family_coverage({m: n for m, n in names.items()})
+    print("[raster64] decided (inside, outside) pairs per mesh:", per_mesh)
+    assert all(a > 0 and b > 0 for n, (a, b) in per_mesh.items() if n not in ("7 degenerate", "7 back-facing")), per_mesh
+    mesh_of_tri, by_name = r.mesh_index[r.tcl], {v: k for k, v in names.items()}
+    assert (r.state[mesh_of_tri == by_name["7 back-facing"]] == raster64.CULLED).all()
+    assert (r.state[mesh_of_tri == by_name["7 degenerate"]] == raster64.UNDECIDED).all()
+    six = r.state[mesh_of_tri == by_name["6 behind the eye"]]
+    assert list(six) == [raster64.CULLED, raster64.CULLED, raster64.UNDECIDED, raster64.DRAWN, raster64.DRAWN] and r.stats["unbounded_triangles"] == 1
+    assert r.reverse.sum() == 7 and r.stats["skipped_clusters"] == 0
+    # rectangle widths of family 5 as the vote sees them
+    widths = lambda name: set((r.hi[:, 0] - r.lo[:, 0] + 1)[(mesh_of_tri == by_name[name]) & (r.es < 1e-2)])
+    assert widths("5 narrow wave") <= {1, 2, 3, 4} and widths("5 wide wave") <= {5, 6, 7, 8} and len(widths("5 one wide among narrow") - {1, 2, 3, 4}) == 1
+
+
+@pytest.mark.parametrize("split", [None, "band"])
+def test_oracle_visibility_of_the_adversarial_scene_against_the_float64_rasteriser(split, adversarial):
+    """The oracle's keys and depth plane on the scene aimed at a rasteriser's weak places (tests/raster64.py: adversarial_scene), whole frame and
+    split in two bands through family 10, against the float64 rasteriser written from softwareRaster.hlsl alone: no stray writes, the depth of
+    the named triangle within the derived bound, nothing nearer missed, no certain coverage left empty, the depth plane the key's depth."""
+    import raster64
+    sc, names, intended, f, r = adversarial
+    g = f if split is None else _oracle_visibility(sc, split=raster64.ADVERSARIAL_SPLIT)
+    figures = raster64.check_visibility(r, g.vis, g.depth, f"adversarial scene ({'whole' if split is None else 'two bands'})")
+    print("[raster64]", figures, "largest barycentric bound of an inside pair:", r.largest_inside_bound)
+    assert figures["checked"] == figures["covered"] > 100000 and np.array_equal(g.vis, f.vis)
+
+
+def test_oracle_visibility_under_a_scissor_smaller_than_the_image_against_the_float64_rasteriser():
+    """The adversarial scene with the view's scissor set inside the image: the screen position maps ndc onto the scissor rectangle (visWidth =
+    scissorMax - scissorMin, + scissorMin), the rectangle is clamped to [scissorMin, scissorMax - 1] and family 4's clamped triangles straddle
+    the scissor's four sides.  Nothing is written outside the scissor, every row and column just inside it is, and the checker's assertions hold
+    (caps as for the unscissored scene)."""
+    import raster64
+    x0, y0, x1, y1 = raster64.ADVERSARIAL_SCISSOR
+    sc, names, _ = raster64.adversarial_scene(scissor=raster64.ADVERSARIAL_SCISSOR)
+    f = _oracle_visibility(sc)
+    r = raster64.Raster64(sc, f.clusters[: f.count])
+    assert (r.scissor == list(raster64.ADVERSARIAL_SCISSOR)).all()
+    raster64.caps_hold(r, 0.15, "adversarial scene, scissored")
+    # from the float64 side alone: triangles certainly cover pixels of the first and the last column and row of the scissor, none beyond
+    sure = np.zeros(sc.width * sc.height, bool); sure[r.p_pix[r.p_verdict == raster64.INSIDE]] = True
+    sure = sure.reshape(sc.height, sc.width)
+    assert sure[:, x0].any() and sure[:, x1 - 1].any() and sure[y0].any() and sure[y1 - 1].any()
+    walked = np.zeros(sc.width * sc.height, bool); walked[r.p_pix] = True
+    walked = walked.reshape(sc.height, sc.width)
+    assert not walked[:, :x0].any() and not walked[:, x1:].any() and not walked[:y0].any() and not walked[y1:].any()
+    mesh_of_tri = r.mesh_index[r.tcl]
+    four = mesh_of_tri == {v: k for k, v in names.items()}["4 clamped"]
+    lo, hi = r.lo[four & r.live], r.hi[four & r.live]
+    assert (lo[:, 0] == x0).sum() >= 2 and (hi[:, 0] == x1 - 1).sum() >= 2 and (lo[:, 1] == y0).sum() >= 2 and (hi[:, 1] == y1 - 1).sum() >= 2
+    figures = raster64.check_visibility(r, f.vis, f.depth, "adversarial scene, scissored")
+    print("[raster64]", figures)
+    covered = f.vis != EMPTY
+    assert figures["checked"] == figures["covered"] > 80000
+    assert not covered[:, :x0].any() and not covered[:, x1:].any() and not covered[:y0].any() and not covered[y1:].any()
+    assert covered[:, x0].any() and covered[:, x1 - 1].any() and covered[y0].any() and covered[y1 - 1].any()
+
+
+@pytest.mark.parametrize("case", ["caller_meshes", "tiny_lod", "sponza_small", "bistro_mirrored_sparser", "sponza_ownlod", "sponza_clod"])
+def test_oracle_visibility_against_the_float64_rasteriser(case, scenes):
+    """The same assertions on the scenes the parity tests use (none skinned, none alpha-tested), whole frame and split in two bands.  Caps from
+    the float64 side alone: undecided pairs <= 2 % of the inside pairs, pixels resting on one <= 2 % of the covered pixels.  The mirrored bistro
+    is the conftest case `bistro_mirrored` at half its size_scale: at 0.3 its distant sub-pixel triangles put the first share at 2.10 % (1.82 % of
+    the pixels), above the cap with the derived bound, so the input was changed and the cap was not; at 0.15 the shares are 1.85 % and 1.64 %."""
+    import raster64
+    from conftest import caller_mesh_scene, have_clodref
+    if case == "sponza_clod" and not have_clodref():
+        pytest.skip("the reference's LOD builder is not built here")
+    if case == "bistro_mirrored_sparser":
+        from conftest import Scene
+        sc = Scene("bistro", 640, 360, point_lights=16, size_scale=0.15, material_features=4)
+    else:
+        sc = caller_mesh_scene() if case == "caller_meshes" else scenes(case)
+    f = _oracle_visibility(sc)
+    r = raster64.Raster64(sc, f.clusters[: f.count])
+    raster64.caps_hold(r, 0.02, case)
+    assert r.stats["skipped_clusters"] == 0 and r.stats["unbounded_triangles"] == 0 and (case != "bistro_mirrored_sparser" or r.reverse.sum() > 100)
+    figures = raster64.check_visibility(r, f.vis, f.depth, case)
+    print("[raster64]", case, figures)
+    assert figures["checked"] == figures["covered"] > 0.3 * sc.width * sc.height
+    g = _oracle_visibility(sc, split=sc.height // 2 - 3)
+    raster64.check_visibility(r, g.vis, g.depth, case + " (two bands)")
+    assert np.array_equal(g.vis, f.vis)
+
+
+def test_float64_rasteriser_agrees_with_exact_arithmetic_where_it_decides(adversarial):
+    """The restatement checks itself where an exact answer exists: families 1 (vertices and edges on pixel centres) and 7 (degenerate, nearly
+    degenerate, back-facing) once more in rationals from the fp32 screen positions: the sign of twiceArea and, per pixel centre, the three edge
+    tests.  Wherever the float64 verdict is decided it is the exact one; on the aimed centres it must be undecided, not wrong."""
+    import raster64
+    sc, names, intended, f, r = adversarial
+    mesh_of_tri = r.mesh_index[r.tcl]
+    chosen = np.flatnonzero(np.isin(mesh_of_tri, [m for m, n in names.items() if _family(n) in ("1", "7")]) & ~r.unbounded)
+    assert len(chosen) == 2 * 8 + 4 + 2 + 1
+    decided_pixels = undecided_pixels = 0
+    for t in chosen:
+        sign, pixels = raster64.exact_verdicts(r, t)
+        if r.state[t] == raster64.DRAWN:
+            assert sign < 0
+        elif r.state[t] == raster64.CULLED:
+            assert sign >= 0
+        if r.state[t] != raster64.DRAWN:
+            continue
+        mine = {int(p): int(v) for p, v in zip(r.p_pix[r.p_tri == t], r.p_verdict[r.p_tri == t])}
+        for p, inside in pixels.items():
+            verdict = mine.get(p, 0)                                   # 0: OUTSIDE (not kept)
+            if verdict == raster64.PIXEL_UNDECIDED:
+                undecided_pixels += 1
+            else:
+                decided_pixels += 1
+                assert (verdict == raster64.INSIDE) == inside, f"triangle {r.tti[t]} of '{names[int(mesh_of_tri[t])]}', pixel ({p % r.W}, {p // r.W})"
+    print(f"[raster64] exact arithmetic: {decided_pixels} decided pixels agree, {undecided_pixels} undecided")
+    assert decided_pixels > 5000 and undecided_pixels >= 2 * 2 * 19        # at least the 19 centres on the first shared diagonal, for both triangles, in both instances

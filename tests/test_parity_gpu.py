@@ -2157,3 +2157,163 @@ def test_adaptive_switch_sweep(case):
     print(f"[sweep] case {case}: held " + " ".join(str(s["held"]) for s in states) + " | lean " + " ".join(str(s["lean"]) for s in states))
     hold, lean = [s["held"] > 0 for s in states[1:]], [s["lean"] for s in states[1:]]
     assert len(set(hold)) > 1 or len(set(lean)) > 1, f"{desc}: neither the draw list nor the lean rasteriser changed state (held {[s['held'] for s in states]}, lean {lean})"
+
+
+# ---- the adversarial raster scene (tests/raster64.py): every raster path against the oracle AND the float64 rasteriser -----------------------
+@pytest.fixture(scope="module")
+def adversarial_frames():
+    import orc
+    import raster64
+    sc, names, _ = raster64.adversarial_scene()
+    o = orc.OracleFrame(sc).run()
+    return sc, names, o, raster64.Raster64(sc, o.clusters[: o.count])
+
+
+def test_adversarial_raster_scene_matches_the_oracle_and_the_float64_rasteriser(adversarial_frames):
+    """The scene aimed at a rasteriser's weak places (vertices and edges on pixel centres, needles, sub-pixel and screen-sized triangles, rectangles
+    on both sides of the wave vote, vertices behind the eye, degenerate, coplanar, mirrored, a stack across a band edge) through the kernels: cluster
+    list, keys, depth and G-buffer exact against the oracle, HDR within one fp16 ULP -- and the GPU's own keys and depth plane through the checker of
+    the float64 rasteriser written from the shader alone."""
+    import raster64
+    from basicrenderer_amd.renderer import VisibilityRenderer
+    sc, names, o, r64 = adversarial_frames
+    r = VisibilityRenderer(sc, stats=True)
+    r.execute()
+    c = r.counters()
+    assert c.droppedRecords == 0 and c.droppedClusters == 0 and o.count == len(names) + 7        # one cluster per mesh, seven mirrored instances
+    assert np.array_equal(r.visible_clusters(), o.clusters[: o.count])
+    vis, depth = r.visibility(), r.depth()
+    raster64.caps_hold(r64, 0.15, "adversarial scene")
+    print("[raster64]", raster64.check_visibility(r64, vis, depth, "adversarial scene, GPU keys"))
+    assert np.array_equal(vis, o.vis)
+    assert np.array_equal(depth.view(np.uint32), o.depth.view(np.uint32))
+    covered = o.vis != np.uint64(0xFFFFFFFFFFFFFFFF)
+    g = r.gbuffer()
+    for key, ref in (("normals", o.normals), ("albedo", o.albedo), ("coat", o.coat), ("emissive", o.emissive), ("fuzz", o.fuzz), ("mr", o.mr), ("motion", o.motion)):
+        a, b = g[key][covered], ref[covered]
+        assert np.array_equal(a.view(np.uint32) if a.dtype == np.float32 else a, b.view(np.uint32) if b.dtype == np.float32 else b), key
+    a, b = r.hdr().view(np.uint16).astype(np.int32), o.hdr.view(np.uint16).astype(np.int32)
+    assert np.abs(a - b).max() <= 1
+    r.close()
+
+
+ADVERSARIAL_PATHS = {
+    # name: (tuning, occlusion culling, frames, what the counters must show)
+    "everything binned": (dict(BRMI_BIG_TRI_AREA=1), False, 1, None),
+    "nothing binned": (dict(BRMI_BIG_TRI_AREA=1 << 30), False, 1, None),
+    "bins of three, overflow queue": (dict(BRMI_BIN_CAPACITY=3, BRMI_BIN_OVERFLOW=16384), False, 1, "overflow"),
+    "bins of three, queue of two": (dict(BRMI_BIN_CAPACITY=3, BRMI_BIN_OVERFLOW=2), False, 1, "overflow"),
+    "bins of three, no queue": (dict(BRMI_BIN_CAPACITY=3, BRMI_BIN_OVERFLOW=0), False, 1, None),
+    "slices of 32": (dict(BRMI_BIN_MIN_SLICE=32, BRMI_BIN_SHARED_SLICE=32, BRMI_BIN_GRID=1024, BRMI_BIN_SCRATCH_TILES=2048), False, 2, None),
+    "slices of 32, pool of eight": (dict(BRMI_BIN_MIN_SLICE=32, BRMI_BIN_SHARED_SLICE=32, BRMI_BIN_GRID=8, BRMI_BIN_SCRATCH_TILES=2048), False, 2, None),
+    "five scratch tiles": (dict(BRMI_BIN_MIN_SLICE=64, BRMI_BIN_SHARED_SLICE=32, BRMI_BIN_GRID=3, BRMI_BIN_SCRATCH_TILES=5), False, 2, None),
+    "no scratch tiles": (dict(BRMI_BIN_MIN_SLICE=32, BRMI_BIN_SHARED_SLICE=32, BRMI_BIN_GRID=1024, BRMI_BIN_SCRATCH_TILES=0), False, 2, None),
+    "slices of 96": (dict(BRMI_BIN_MIN_SLICE=96, BRMI_BIN_SHARED_SLICE=64, BRMI_BIN_GRID=300, BRMI_BIN_SCRATCH_TILES=2048), False, 2, None),
+    "occlusion culling": (dict(), True, 2, None),
+    "wide pass": (dict(wide_min_triangles=1, wide_entries=16), True, 3, "wide"),
+    "wide pass, queue of two": (dict(wide_min_triangles=1, wide_entries=16, wide_capacity=2), True, 3, "wide"),
+    "lean rasteriser": (dict(lean_min_clusters=1, lean_max_general_pct=100), True, 4, "lean"),
+    "lean rasteriser, queue of 64, wide emission": (dict(lean_min_clusters=1, lean_max_general_pct=100, lean_queue=64, wide_min_triangles=1, wide_entries=16, lean_wide_entries=2), True, 4, "lean overflow"),
+}
+
+
+@pytest.mark.parametrize("path", list(ADVERSARIAL_PATHS))
+def test_adversarial_raster_scene_through_every_forced_raster_path(path, adversarial_frames):
+    """The same scene with each raster path forced the way the tests above force it on the generator's scenes -- everything / nothing binned, bins of
+    three records with and without an overflow queue, the bin plan's slice, pool and scratch-tile settings, occlusion culling (two phases), the
+    wide-triangle pass and the lean rasteriser: the oracle's keys every time (by what they name where two phases reorder the list), through the
+    float64 checker too, and the counters show that the forced path ran."""
+    import orc
+    import raster64
+    import torch
+    from basicrenderer_amd.renderer import VisibilityRenderer
+    sc, names, o, r64 = adversarial_frames
+    tun, occlusion, frames, counter = ADVERSARIAL_PATHS[path]
+    with _Env(**tun):
+        r = VisibilityRenderer(sc, stats=True, occlusion=occlusion)
+    for _ in range(frames):
+        r.update(); r.execute()
+        torch.cuda.synchronize()
+        c = r.counters()
+        assert c.droppedRecords == 0 and c.droppedClusters == 0
+        vis, lists = r.visibility(), r.visible_clusters()
+        if occlusion:
+            for got, want in zip(orc.canonical_ids(vis, lists), orc.canonical_ids(o.vis, o.clusters[: o.count])):
+                assert np.array_equal(got, want), path
+        else:
+            assert np.array_equal(vis, o.vis), path
+    if occlusion:
+        r64 = raster64.Raster64(sc, lists)                    # the two phases list the clusters in their own order
+    raster64.check_visibility(r64, vis, r.depth(), f"adversarial scene, {path}")
+    if counter == "overflow":
+        assert c.reserved[5] > 0, "no bin overflowed"
+    elif counter == "wide":
+        assert sum(r.wide_triangles()) > 0, "no triangle took the wide pass"
+    elif counter in ("lean", "lean overflow"):
+        on, general, queued, runs = r.lean_clusters()
+        assert on == 1 and queued > 0, "the lean rasteriser did not run, or queued no triangle for the emission"
+        if counter == "lean overflow":
+            assert general > 0, "a queue of 64 triangles did not overflow"
+            assert sum(r.wide_triangles()) > 0, "the emission handed no triangle to the wide pass"
+    r.close()
+
+
+def test_adversarial_raster_scene_in_two_bands_and_in_interleaved_stripes(adversarial_frames):
+    """Split in two row bands through the stack of family 10, and (at a height the stripes divide) in interleaved chunks of 16 rows for two ranks: what
+    the keys name, the depth bits and the depth plane are the full frame's on every rank's rows; the bands, put together, pass the float64 checker."""
+    import orc
+    import raster64
+    from basicrenderer_amd.renderer import VisibilityRenderer
+    sc, names, o, r64 = adversarial_frames
+    want = orc.canonical_ids(o.vis, o.clusters[: o.count])
+    for y0, y1 in ((0, raster64.ADVERSARIAL_SPLIT), (raster64.ADVERSARIAL_SPLIT, sc.height)):
+        r = VisibilityRenderer(sc, band=(y0, y1))
+        r.execute()
+        vis, lists = r.visibility(), r.visible_clusters()
+        for got, ref in zip(orc.canonical_ids(vis, lists), want):
+            assert np.array_equal(got[y0:y1], ref[y0:y1]), (y0, y1)
+        assert np.array_equal(r.depth().view(np.uint32)[y0:y1], o.depth.view(np.uint32)[y0:y1])
+        # the band's own keys and list through the checker, on its rows (the rows of the other band read as empty there)
+        mine = np.full_like(vis, raster64.EMPTY); mine[y0:y1] = vis[y0:y1]
+        raster64.check_visibility(raster64.Raster64(sc, lists).restricted_to_rows(y0, y1), mine, None, f"adversarial scene, band {y0}-{y1}")
+        r.close()
+    sc2, _, _ = raster64.adversarial_scene(size=(700, 416))
+    o2 = orc.OracleFrame(sc2); o2.cull(); o2.raster(); o2.depth_copy()
+    want = orc.canonical_ids(o2.vis, o2.clusters[: o2.count])
+    for index in range(2):
+        r = VisibilityRenderer(sc2, stripes=(16, 2, index))
+        r.execute()
+        fr = r.frame_rows()
+        for got, ref in zip(orc.canonical_ids(r.visibility(), r.visible_clusters()), want):
+            assert np.array_equal(got, ref[fr]), f"rank {index}"
+        assert np.array_equal(r.depth().view(np.uint32), o2.depth.view(np.uint32)[fr])
+        r.close()
+
+
+def test_adversarial_raster_scene_under_a_scissor_smaller_than_the_image():
+    """The view's scissor set inside the image (ndc mapped onto the scissor rectangle, rectangles clamped to it, family 4 straddling its four sides):
+    cluster list, keys and depth exact against the oracle, direct and with everything binned, nothing outside the scissor, and the GPU's keys
+    through the float64 checker."""
+    import orc
+    import raster64
+    from basicrenderer_amd.renderer import VisibilityRenderer
+    x0, y0, x1, y1 = raster64.ADVERSARIAL_SCISSOR
+    sc, names, _ = raster64.adversarial_scene(scissor=raster64.ADVERSARIAL_SCISSOR)
+    o = orc.OracleFrame(sc); o.cull(); o.raster(); o.depth_copy()
+    r64 = raster64.Raster64(sc, o.clusters[: o.count])
+    raster64.caps_hold(r64, 0.15, "adversarial scene, scissored")
+    for tun in (dict(), dict(BRMI_BIG_TRI_AREA=1), dict(BRMI_BIG_TRI_AREA=1 << 30)):
+        with _Env(**tun):
+            r = VisibilityRenderer(sc, stats=True)
+        r.execute()
+        c = r.counters()
+        assert c.droppedRecords == 0 and c.droppedClusters == 0
+        assert np.array_equal(r.visible_clusters(), o.clusters[: o.count]), tun
+        vis, depth = r.visibility(), r.depth()
+        print("[raster64]", raster64.check_visibility(r64, vis, depth, f"adversarial scene, scissored, GPU keys {tun}"))
+        assert np.array_equal(vis, o.vis), tun
+        assert np.array_equal(depth.view(np.uint32), o.depth.view(np.uint32)), tun
+        covered = vis != raster64.EMPTY
+        assert not covered[:, :x0].any() and not covered[:, x1:].any() and not covered[:y0].any() and not covered[y1:].any()
+        assert covered[:, x0].any() and covered[:, x1 - 1].any() and covered[y0].any() and covered[y1 - 1].any()
+        r.close()
