@@ -120,6 +120,12 @@ class FrameUpdate(C.Structure):
     _fields_ = [("mainCameraHost", vp), ("perFrameHost", vp), ("frameIndex", u32)]
 
 
+class StreamingBuffers(C.Structure):
+    """brmi_streaming_buffers (include/brmi.h): caller-owned device memory of the residency-aware cut and its feedback."""
+    _fields_ = [("structSize", u32), ("activeGroupScanCount", u32), ("nonResidentBits", vp), ("loadRequests", vp), ("requestCapacity", u32),
+                ("touchedGroups", vp), ("touchedCapacity", u32), ("counts", vp), ("scratch", vp), ("scratchBytes", u64)]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, u32) for n in ("instancesTested instancesVisible nodesVisited bucketRecords meshletsTested "
                                    "visibleClusters visibleClustersPhase2 droppedRecords droppedClusters "
@@ -222,7 +228,8 @@ def scene_lib():
 BRMI_EXPORTS = ["brmi_abi_version", "brmi_default_config", "brmi_create", "brmi_declare", "brmi_set_scene", "brmi_setup", "brmi_set_band",
                 "brmi_update", "brmi_execute", "brmi_execute_split", "brmi_destroy", "brmi_last_error", "brmi_clear_visibility", "brmi_cull",
                 "brmi_raster", "brmi_depth_copy", "brmi_build_hzb", "brmi_invalidate_hzb", "brmi_set_history_source", "brmi_gbuffer", "brmi_light_clustering",
-                "brmi_shade", "brmi_set_shade_slabs", "brmi_read_counters", "brmi_stage_times", "brmi_set_timed_stages", "brmi_algorithmic_bytes", "brmi_algorithmic_bytes_launched", "brmi_debug_arith", "brmi_debug_arith_in_range", "brmi_debug_read_bin_records", "brmi_debug_wide_triangles", "brmi_debug_lean_clusters", "brmi_debug_read_lean_queue", "brmi_debug_read_held"]
+                "brmi_shade", "brmi_set_shade_slabs", "brmi_read_counters", "brmi_stage_times", "brmi_set_timed_stages", "brmi_algorithmic_bytes", "brmi_algorithmic_bytes_launched", "brmi_debug_arith", "brmi_debug_arith_in_range", "brmi_debug_read_bin_records", "brmi_debug_wide_triangles", "brmi_debug_lean_clusters", "brmi_debug_read_lean_queue", "brmi_debug_read_held",
+                "brmi_streaming_scratch_bytes", "brmi_set_streaming", "brmi_streaming_feedback"]
 
 
 def brmi_lib():
@@ -265,5 +272,9 @@ def brmi_lib():
         lib.brmi_algorithmic_bytes_launched.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
         lib.brmi_debug_arith.argtypes = [vp, vp, vp, vp, vp, u32, vp]
         lib.brmi_debug_arith_in_range.argtypes = [vp, vp, vp, vp, u32, vp]
+        lib.brmi_streaming_scratch_bytes.argtypes = [u32]
+        lib.brmi_streaming_scratch_bytes.restype = u64
+        lib.brmi_set_streaming.argtypes = [vp, C.POINTER(StreamingBuffers)]
+        lib.brmi_streaming_feedback.argtypes = [vp, vp]
         _brmi_lib = lib
     return _brmi_lib

@@ -309,6 +309,7 @@ const char* brmi_last_error(const brmi_pass* p) { return p ? p->err.c_str() : "n
 int brmi_set_scene(brmi_pass* p, const brmi_scene_buffers* scene) {
     if (!p || !scene) return BRMI_ERR_INVALID;
     p->scene = *scene; p->haveScene = false; p->setupDone = false;
+    p->streaming.on = false;      // (bound to the group table of the scene before: brmi_set_streaming again)
     const brmi_scene_buffers& sc = p->scene;
     if (!sc.slabs || !sc.perObject || !sc.perMesh || !sc.perMeshInstance || !sc.clodOffsets || !sc.meshMetadata || !sc.lodNodes || !sc.lodGroups ||
         !sc.lodSegments || !sc.groupPageMap || !sc.materials || !sc.openpbrMaterials || !sc.cameras || !sc.cullingCameras || !sc.viewRasterInfo || !sc.perFrame ||
@@ -502,8 +503,8 @@ int brmi_set_scene(brmi_pass* p, const brmi_scene_buffers* scene) {
                 if (nd.isLeaf == BRMI_NODE_INTERNAL) f.info |= 1u;
                 else {
                     const brmi_lod_group& g = groups[md[m].groupsBase + nd.ownerGroupId];
-                    std::memcpy(l.group, g.centerAndRadius, 16);
-                    if (nd.countMinusOne != 0u) { const brmi_lod_group& cg = groups[md[m].groupsBase + (nd.countMinusOne - 1u)]; std::memcpy(l.child, cg.centerAndRadius, 16); l.childParentError = cg.maxParentError; f.info |= 1u << 1; }
+                    std::memcpy(l.group, g.centerAndRadius, 16); l.ownerGlobal = md[m].groupsBase + nd.ownerGroupId;
+                    if (nd.countMinusOne != 0u) { const brmi_lod_group& cg = groups[md[m].groupsBase + (nd.countMinusOne - 1u)]; std::memcpy(l.child, cg.centerAndRadius, 16); l.childParentError = cg.maxParentError; l.childGlobal = md[m].groupsBase + (nd.countMinusOne - 1u); f.info |= 1u << 1; }
                     const size_t si = (size_t)md[m].segmentsBase + nd.indexOrOffset;
                     if (si >= segs.size()) return fail(p, BRMI_ERR_INVALID, "mesh %zu: leaf node %u names segment %u, which does not exist", m, bfs[k].first, nd.indexOrOffset);
                     if (segs[si].meshletCount != 0u) f.info |= 1u << 2;
@@ -740,6 +741,27 @@ int brmi_depth_copy(brmi_pass* p, brmi_stream stream) {
     CHECK_READY(p); hipStream_t s = static_cast<hipStream_t>(stream);
     STAGE_BEGIN(p, BRMI_STAGE_DEPTH_COPY, s); int rc = launch_depth_copy(p, s); STAGE_END(p, BRMI_STAGE_DEPTH_COPY, s); return rc;
 }
+uint64_t brmi_streaming_scratch_bytes(uint32_t lodGroupCount) { return brmi::stream_scratch_layout(lodGroupCount).total; }
+int brmi_set_streaming(brmi_pass* p, const brmi_streaming_buffers* b) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (!b) { p->streaming.on = false; return BRMI_OK; }
+    if (!p->haveScene) return brmi::fail(p, BRMI_ERR_STATE, "brmi_set_streaming: brmi_set_scene first (the buffers are sized by its group table)");
+    if (b->structSize != sizeof(brmi_streaming_buffers)) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_streaming: structSize %u, expected %zu", b->structSize, sizeof(brmi_streaming_buffers));
+    if (!b->nonResidentBits || !b->counts || !b->scratch || (b->requestCapacity && !b->loadRequests) || (b->touchedCapacity && !b->touchedGroups))
+        return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_streaming: a required streaming buffer is null");
+    const uint64_t need = brmi_streaming_scratch_bytes(p->scene.lodGroupCount);
+    if (b->scratchBytes < need) return brmi::fail(p, BRMI_ERR_CAPACITY, "brmi_set_streaming: scratch holds %llu bytes, %u groups need %llu", (unsigned long long)b->scratchBytes, p->scene.lodGroupCount, (unsigned long long)need);
+    if (reinterpret_cast<uintptr_t>(b->scratch) & 15u) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_streaming: scratch must be 16 B aligned");
+    p->streaming.b = *b; p->streaming.groupCount = p->scene.lodGroupCount;
+    p->streaming.activeGroupScanCount = std::min(b->activeGroupScanCount, p->scene.lodGroupCount);
+    p->streaming.on = true;
+    return BRMI_OK;
+}
+int brmi_streaming_feedback(brmi_pass* p, brmi_stream stream) {
+    CHECK_READY(p);
+    if (!p->streaming.on) return brmi::fail(p, BRMI_ERR_STATE, "brmi_streaming_feedback: no streaming buffers bound (brmi_set_streaming)");
+    return brmi::launch_streaming_feedback(p, static_cast<hipStream_t>(stream));
+}
 int brmi_build_hzb(brmi_pass* p, brmi_stream stream) {
     CHECK_READY(p); hipStream_t s = static_cast<hipStream_t>(stream);
     if (!p->cfg.enableOcclusionCulling) return brmi::fail(p, BRMI_ERR_STATE, "brmi_build_hzb: the pass was created without enableOcclusionCulling");
@@ -868,6 +890,8 @@ int brmi_execute_split(brmi_pass* p, brmi_stream stream, brmi_stream shadeStream
         BRMI_HIP(p, hipEventRecord(p->chainReady, static_cast<hipStream_t>(stream)));
         p->chainRecorded = true; p->chainStream = stream;
     }
+    // CLodStreamingFeedbackSortPass, behind the frame's last culling phase on the geometry stream (behind the chain event: a linked pass's next frame does not wait for it)
+    if (p->streaming.on && (rc = brmi_streaming_feedback(p, stream))) return rc;
     if (split) {
         if ((rc = launch_resolve_setup(p, static_cast<hipStream_t>(stream), 2u))) return rc;
         p->resolveSetupDone = true;

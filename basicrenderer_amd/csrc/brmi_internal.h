@@ -90,7 +90,7 @@ struct FlatNode {                                                               
     uint32_t firstBitRel;       // leaf: the segment's first bit relative to the instance's
     uint32_t children;          // internal: position of the first child | child count << 16 (breadth-first: a node's children sit side by side)
 };
-struct FlatLeaf { float group[4], child[4]; float childParentError, pad[3]; };      // 48 B: the leaf's group sphere, its refined group's sphere and error
+struct FlatLeaf { float group[4], child[4]; float childParentError; uint32_t ownerGlobal, childGlobal /* indices into lodGroups: what the residency rule looks up (brmi_set_streaming) */, pad; };      // 48 B: the leaf's group sphere, its refined group's sphere and error
 struct InstanceWalk { uint32_t flatBase, flatCount /* 0: the level walk */, bitBase, skinned; };                                    // 16 B per mesh instance
 static_assert(sizeof(FlatNode) == 64 && sizeof(FlatLeaf) == 48 && sizeof(InstanceWalk) == 16, "flat traversal records");
 struct NodeRecord { uint32_t instanceIndex, nodeIdPacked; };                       // 8 B (single view)
@@ -217,6 +217,26 @@ __device__ __forceinline__ bool box_behind_chain(const HzbDesc& hzb, const Meshl
         if (!(farthest < nearSafe)) return false;
     }
     return true;
+}
+
+// ---- residency-aware cut and streaming feedback (brmi_set_streaming, brmi_cull.hip) ----
+// What the culling kernels get when streaming is on: the caller's residency bits and, in the caller's scratch, a touched bit and a best-request word per group.
+struct StreamArgs { const uint32_t* nonResidentBits; uint32_t* touchedBits; unsigned long long* requestKeys; uint32_t activeGroupScanCount /* <= groupCount */, groupCount; };
+// byte offsets into brmi_streaming_buffers::scratch: [0, frameBytes) is zeroed when a frame's culling starts
+struct StreamScratchLayout { uint64_t touchedBits, requestKeys, frameBytes, listA, listB, total; };
+inline StreamScratchLayout stream_scratch_layout(uint32_t groupCount) {
+    StreamScratchLayout l{};
+    const uint64_t g = groupCount ? groupCount : 1u;
+    l.touchedBits = 0; l.requestKeys = (((g + 31u) / 32u * 4u) + 15u) & ~15ull; l.frameBytes = l.requestKeys + g * 8u;
+    l.listA = (l.frameBytes + 15u) & ~15ull; l.listB = l.listA + ((g * 4u + 15u) & ~15ull); l.total = l.listB + ((g * 4u + 15u) & ~15ull);
+    return l;
+}
+// CLodPackViewPriority's quantisation (workGraphCulling.hlsl:1012-1018): round(clamp(errorOverDistance * 1024, 0, 65535)); NaN and negatives give 0
+__host__ __device__ inline uint32_t stream_priority16(float errorOverDistance) {
+    float c = errorOverDistance * 1024.0f;
+    c = c > 0.0f ? c : 0.0f;
+    c = c < 65535.0f ? c : 65535.0f;
+    return (uint32_t)(c + 0.5f);
 }
 
 // Scenes whose materials all pack to the same coat (fuzz) G-buffer word: the word and whether the plane currently holds it everywhere
@@ -357,6 +377,7 @@ struct brmi_pass {
     std::vector<uint32_t> hostInstanceBitBase, hostSegPrefix;
     std::vector<brmi::FlatNode> hostFlatNodes; std::vector<brmi::FlatLeaf> hostFlatLeaves; std::vector<brmi::InstanceWalk> hostInstanceWalk;   // flat traversal tables (brmi_set_scene)
     brmi::Workspace ws{};
+    struct { bool on = false; brmi_streaming_buffers b{}; uint32_t groupCount = 0, activeGroupScanCount = 0; } streaming;      // brmi_set_streaming (cleared by brmi_set_scene)
     brmi_camera camHost{};
     brmi_per_frame pfHost{};
     std::vector<float> planesHost;
@@ -399,6 +420,13 @@ int launch_light_clustering(brmi_pass* p, hipStream_t s);
 int launch_expand_luts(brmi_pass* p, hipStream_t s);
 int launch_meshlet_boxes(brmi_pass* p, hipStream_t s);      // brmi_setup: the per-meshlet boxes of the draw list's tests, from the page contents
 int launch_shade(brmi_pass* p, hipStream_t s);
+int launch_streaming_feedback(brmi_pass* p, hipStream_t s);
+inline StreamArgs stream_args_of(const brmi_pass* p) {
+    if (!p->streaming.on) return StreamArgs{nullptr, nullptr, nullptr, 0u, 0u};
+    const StreamScratchLayout l = stream_scratch_layout(p->streaming.groupCount);
+    uint8_t* scratch = static_cast<uint8_t*>(p->streaming.b.scratch);
+    return StreamArgs{p->streaming.b.nonResidentBits, reinterpret_cast<uint32_t*>(scratch + l.touchedBits), reinterpret_cast<unsigned long long*>(scratch + l.requestKeys), p->streaming.activeGroupScanCount, p->streaming.groupCount};
+}
 
 }  // namespace brmi
 #endif

@@ -264,6 +264,73 @@ class VisibilityRenderer:
         self._slab_cb = proto(trampoline)      # kept alive with the pass
         self._check(self.lib.brmi_set_shade_slabs(self._h, capi.u32(slabs), C.cast(self._slab_cb, C.c_void_p), None), "brmi_set_shade_slabs")
 
+    # -- residency-aware cut and streaming feedback (brmi_set_streaming) ---------------------------
+    def group_count(self):
+        return int(self.sb.lodGroupCount)
+
+    def set_streaming(self, non_resident_groups, active_group_scan_count=None, request_capacity=1 << 16, touched_capacity=1 << 17):
+        """The cut follows residency from the next frame on: `non_resident_groups` (indices into lodGroups, or a bool mask over them) are not resident, groups
+        at or above `active_group_scan_count` (default: the group count) neither, and those are never requested.  None switches streaming off.  The buffers
+        (residency bits, request and touched lists, counts, scratch) are this pass's own tensors; calling it again with the same capacities rewrites the
+        residency bits in place on the current stream, so frames in flight keep the bits they were issued with."""
+        torch = self.torch
+        if non_resident_groups is None:
+            self._check(self.lib.brmi_set_streaming(self._h, None), "brmi_set_streaming")
+            self._streaming = None
+            return
+        groups = self.group_count()
+        mask = np.zeros(((groups + 31) // 32) * 32, dtype=bool)
+        nr = np.asarray(non_resident_groups)
+        if nr.dtype == bool:
+            mask[:groups] = nr
+        elif nr.size:
+            mask[nr.astype(np.int64)] = True
+        words = np.packbits(mask.reshape(-1, 32), axis=1, bitorder="little").view(np.uint32).reshape(-1)
+        words = np.ascontiguousarray(words if words.size else np.zeros(1, dtype=np.uint32))
+        active = groups if active_group_scan_count is None else int(active_group_scan_count)
+        st = getattr(self, "_streaming", None)
+        if st is not None and st["caps"] == (int(request_capacity), int(touched_capacity)):
+            st["bits"].copy_(torch.from_numpy(words.view(np.int32)), non_blocking=False)
+        else:
+            scratch_bytes = int(self.lib.brmi_streaming_scratch_bytes(groups))
+            st = dict(caps=(int(request_capacity), int(touched_capacity)),
+                      bits=torch.from_numpy(words.view(np.int32)).to(self.device),
+                      requests=torch.zeros((max(1, int(request_capacity)), 4), dtype=torch.int32, device=self.device),
+                      touched=torch.zeros(max(1, int(touched_capacity)), dtype=torch.int32, device=self.device),
+                      counts=torch.zeros(2, dtype=torch.int32, device=self.device),
+                      scratch=torch.zeros(scratch_bytes + 16, dtype=torch.uint8, device=self.device))
+        b = capi.StreamingBuffers()
+        b.structSize = C.sizeof(capi.StreamingBuffers)
+        b.activeGroupScanCount = active
+        b.nonResidentBits = st["bits"].data_ptr()
+        b.loadRequests, b.requestCapacity = st["requests"].data_ptr(), int(request_capacity)
+        b.touchedGroups, b.touchedCapacity = st["touched"].data_ptr(), int(touched_capacity)
+        b.counts = st["counts"].data_ptr()
+        b.scratch, b.scratchBytes = st["scratch"].data_ptr(), st["scratch"].numel()
+        self._check(self.lib.brmi_set_streaming(self._h, C.byref(b)), "brmi_set_streaming")
+        self._streaming = st
+
+    def streaming_tensors(self):
+        """The device tensors behind the feedback (requests [capacity, 4], touched [capacity], counts [2], int32): clone them on the frame's geometry stream
+        to keep a frame's feedback while later frames are in flight."""
+        st = self._streaming
+        return st["requests"], st["touched"], st["counts"]
+
+    @staticmethod
+    def unpack_feedback(requests, touched, counts):
+        counts = np.asarray(counts).view(np.uint32).reshape(2).copy()
+        requests, touched = np.asarray(requests).view(np.uint32), np.asarray(touched).view(np.uint32)
+        return requests[: min(int(counts[0]), len(requests))].copy(), touched[: min(int(counts[1]), len(touched))].copy(), counts
+
+    def streaming_feedback(self):
+        """(requests ndarray[n, 4] of {group, instance, mesh buffer, priority16 << 16 | view}, touched ndarray, counts) of the last frame; n and len(touched)
+        are clamped to the capacities, counts = (requested groups, touched groups) are not.  Waits for the device."""
+        if getattr(self, "_streaming", None) is None:
+            raise BrmiError("streaming_feedback: set_streaming first")
+        self.torch.cuda.synchronize(self.device)
+        r, t, c = self.streaming_tensors()
+        return self.unpack_feedback(r.cpu().numpy(), t.cpu().numpy(), c.cpu().numpy())
+
     def set_history_source(self, other):
         """Frames in flight: phase 1 tests against the depth chain `other` built for the frame before (None unlinks)."""
         self._check(self.lib.brmi_set_history_source(self._h, other._h if other is not None else None), "brmi_set_history_source")

@@ -113,6 +113,27 @@ typedef struct brmi_scene_buffers {
     const float*             srgbToLinear;
 } brmi_scene_buffers;
 
+/* ---- residency and streaming feedback (CLodStreaming*; optional) ------------------------------
+ * With these bound the cluster-LOD cut follows the reference's full rule "... and the refined child group is resident" (workGraphCulling.hlsl:1543-1701,
+ * 1713-1783): a leaf whose own group is not resident is not drawn, a parent whose refined child is not resident keeps drawing, and the culling
+ * kernels record which groups the frame touched and which it wants loaded.  All of it is caller-owned device memory (the library never allocates);
+ * passes that render frames in turn bind their own.
+ *   loadRequests   one record per REQUESTED GROUP (not per requesting thread, as the reference's raw stream has it): the highest priority any request
+ *                  of the frame gave the group, among the requests of that priority the lowest instance index and that instance's perMeshBufferIndex;
+ *                  ordered by descending priority, then ascending group index.  More than requestCapacity: the first requestCapacity of that order.
+ *   touchedGroups  the touched group indices in ascending order, under the same truncation rule.
+ *   counts         [0] = requested groups, [1] = touched groups of the frame, whatever the capacities.
+ * This is what the reference's host makes of its stream after read-back (CLodStreamingSystem::PushOrUpdatePendingStreamingRequest). */
+typedef struct brmi_streaming_buffers {
+    uint32_t structSize;                     /* sizeof(brmi_streaming_buffers) */
+    uint32_t activeGroupScanCount;           /* CLodStreamingRuntimeState: groups at or above it are non-resident and are never requested (clamped to lodGroupCount) */
+    const uint32_t* nonResidentBits;         /* Builtin::CLod::StreamingNonResidentBits: bit g set = group g (index into lodGroups) is not resident; ceil(lodGroupCount / 32) words */
+    brmi_streaming_request* loadRequests;    uint32_t requestCapacity;   /* Builtin::CLod::StreamingLoadRequests (reference: 1 << 16) */
+    uint32_t* touchedGroups;                 uint32_t touchedCapacity;   /* Builtin::CLod::StreamingTouchedGroups (reference: 1 << 17) */
+    uint32_t* counts;                        /* two words: StreamingLoadCounter, StreamingTouchedGroupsCounter */
+    void* scratch;                           uint64_t scratchBytes;      /* >= brmi_streaming_scratch_bytes(lodGroupCount), 16 B aligned; the library's between the frame's first culling launch and brmi_streaming_feedback */
+} brmi_streaming_buffers;
+
 /* ---- graph resources the pass declares (DeclareResourceUsages) ---------------------------- */
 typedef enum brmi_resource_id {
     BRMI_RES_VISIBILITY = 0,          /* Builtin::PrimaryCamera::VisibilityTexture  u64/px, tiled 8x8 */
@@ -213,6 +234,12 @@ int         brmi_execute_split(brmi_pass* pass, brmi_stream geometryStream, brmi
 void        brmi_destroy(brmi_pass* pass);                                               /* Cleanup */
 const char* brmi_last_error(const brmi_pass* pass);
 
+/* Residency-aware cut + streaming feedback.  Call after brmi_set_scene (which forgets the binding: the group table may have changed); NULL switches it off
+ * and gives exactly the frames of a pass that never called it.  Refuses (BRMI_ERR_INVALID / BRMI_ERR_CAPACITY) a null required pointer or scratch that is
+ * too small.  The residency bits are read by the frame's culling launches: rewrite them between frames, in stream order with the frames. */
+uint64_t brmi_streaming_scratch_bytes(uint32_t lodGroupCount);
+int brmi_set_streaming(brmi_pass* pass, const brmi_streaming_buffers* streaming);
+
 /* Rows [bandY0, bandY1) of the frame this GPU renders FROM THE NEXT FRAME ON (multiples of 8; passes created with brmi_config::dynamicBand): call it between frames,
  * before the frame's brmi_update.  The screen-tile split of SURVEY.md 8(e) with regions whose boundaries follow the cost of the frames before, so that every GPU takes
  * the same time: a cluster is set up by the one GPU whose band holds it (two at a boundary), and the band test of the instance / node / cluster culling drops the rest
@@ -227,6 +254,10 @@ int brmi_clear_visibility(brmi_pass* pass, brmi_stream stream);   /* ClearVisibi
 int brmi_cull(brmi_pass* pass, uint32_t phase, brmi_stream stream);       /* HierarchicalCullingPass1/2 (K1-K3) */
 int brmi_raster(brmi_pass* pass, uint32_t phase, brmi_stream stream);     /* SoftwareRasterizeClustersPass1/2 (K5) */
 int brmi_depth_copy(brmi_pass* pass, brmi_stream stream);         /* LinearDepthCopyPass (K6) */
+/* CLodStreamingFeedbackSortPass: compacts and orders what the frame's culling recorded into loadRequests / touchedGroups / counts.  brmi_execute runs it after the
+ * frame's last culling phase, brmi_execute_split on the geometry stream; the frame's first culling launch resets the per-frame state (CLodStreamingBeginFramePass).
+ * BRMI_ERR_STATE without brmi_set_streaming. */
+int brmi_streaming_feedback(brmi_pass* pass, brmi_stream stream);
 int brmi_build_hzb(brmi_pass* pass, brmi_stream stream);          /* LinearDepthDownsamplePass (SPD max-reduce; BR/shaders/downsample.hlsl) */
 /* Drops the previous frame's depth chain (camera cut, resize): the next phase 1 runs without occlusion tests. */
 int brmi_invalidate_hzb(brmi_pass* pass);

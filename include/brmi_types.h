@@ -170,6 +170,15 @@ typedef struct brmi_group_page_map_entry {
     uint32_t slabByteOffset;
 } brmi_group_page_map_entry;
 
+/* CLodStreamingRequest (workGraphCulling.hlsl:1587-1606): a group the frame wants loaded.  viewId: low 16 bits the view, high 16 bits the
+ * quantised priority of CLodPackViewPriority (:1012-1018), round(clamp(errorOverDistance * 1024, 0, 65535)). */
+typedef struct brmi_streaming_request {
+    uint32_t groupGlobalIndex;      /* index into lodGroups */
+    uint32_t meshInstanceIndex;
+    uint32_t meshBufferIndex;       /* perMeshInstance[meshInstanceIndex].perMeshBufferIndex */
+    uint32_t viewId;
+} brmi_streaming_request;                   /* 16 B */
+
 /* BR/shaders/Include/clodStructs.hlsli:4-22 */
 typedef struct brmi_mesh_instance_clod_offsets { uint32_t clodMeshMetadataIndex; } brmi_mesh_instance_clod_offsets;
 typedef struct brmi_clod_mesh_metadata {
