@@ -220,8 +220,45 @@ __device__ __forceinline__ bool box_behind_chain(const HzbDesc& hzb, const Meshl
 }
 
 // ---- residency-aware cut and streaming feedback (brmi_set_streaming, brmi_cull.hip) ----
-// What the culling kernels get when streaming is on: the caller's residency bits and, in the caller's scratch, a touched bit and a best-request word per group.
-struct StreamArgs { const uint32_t* nonResidentBits; uint32_t* touchedBits; unsigned long long* requestKeys; uint32_t activeGroupScanCount /* <= groupCount */, groupCount; };
+// CLodPackViewPriority's quantisation (workGraphCulling.hlsl:1012-1018): round(clamp(errorOverDistance * 1024, 0, 65535)); NaN and negatives give 0
+__host__ __device__ inline uint32_t stream_priority16(float errorOverDistance) {
+    float c = errorOverDistance * 1024.0f;
+    c = c > 0.0f ? c : 0.0f;
+    c = c < 65535.0f ? c : 65535.0f;
+    return (uint32_t)(c + 0.5f);
+}
+// The culling kernels are templates on a residency policy, their trailing argument: resident(group), touch(group, ...) -> resident, and kTracks (the
+// kernel keeps what it needs to touch the leaves it reaches).
+// StreamArgs: what they get when streaming is on -- the caller's residency bits and, in the caller's scratch, a touched bit and a best-request word per
+// group.  The reference appends one record per touching thread to two lists and sorts; here a group has ONE bit ("touched") and ONE 64-bit word (the best
+// request: bit 63 | priority16 << 32 | ~instanceIndex, kept with an atomic max, so the highest priority wins and among equals the lowest instance), and
+// brmi_streaming_feedback compacts and orders them.  Both are looked at before they are written: after a group's first touch of a frame the common case
+// is one load and no atomic.
+struct StreamArgs {
+    const uint32_t* nonResidentBits; uint32_t* touchedBits; unsigned long long* requestKeys; uint32_t activeGroupScanCount /* <= groupCount */, groupCount;
+    static constexpr bool kTracks = true;
+    BRMI_DEV bool resident(uint32_t group) const {
+        return group < activeGroupScanCount && ((nonResidentBits[group >> 5] >> (group & 31u)) & 1u) == 0u;      // (activeGroupScanCount <= the group count: brmi_set_streaming)
+    }
+    // CLodTouchAndRequestGroupResident: marks the group touched, asks for it when it is not resident (never beyond activeGroupScanCount); true = resident
+    BRMI_DEV bool touch(uint32_t group, uint32_t instanceIndex, float errorOverDistance) const {
+        if (group >= groupCount) return false;
+        const uint32_t bit = 1u << (group & 31u);
+        if ((__hip_atomic_load(&touchedBits[group >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit) == 0u) atomicOr(&touchedBits[group >> 5], bit);
+        if (resident(group)) return true;
+        if (group < activeGroupScanCount) {
+            const unsigned long long key = (1ull << 63) | ((unsigned long long)stream_priority16(errorOverDistance) << 32) | (unsigned long long)(~instanceIndex);
+            if (__hip_atomic_load(&requestKeys[group], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < key) atomicMax(&requestKeys[group], key);
+        }
+        return false;
+    }
+};
+// AllResident: a pass without streaming -- every group is there and nothing is recorded (an empty kernel argument, like NoSide)
+struct AllResident {
+    static constexpr bool kTracks = false;
+    BRMI_DEV bool resident(uint32_t) const { return true; }
+    BRMI_DEV bool touch(uint32_t, uint32_t, float) const { return true; }
+};
 // byte offsets into brmi_streaming_buffers::scratch: [0, frameBytes) is zeroed when a frame's culling starts
 struct StreamScratchLayout { uint64_t touchedBits, requestKeys, frameBytes, listA, listB, total; };
 inline StreamScratchLayout stream_scratch_layout(uint32_t groupCount) {
@@ -230,13 +267,6 @@ inline StreamScratchLayout stream_scratch_layout(uint32_t groupCount) {
     l.touchedBits = 0; l.requestKeys = (((g + 31u) / 32u * 4u) + 15u) & ~15ull; l.frameBytes = l.requestKeys + g * 8u;
     l.listA = (l.frameBytes + 15u) & ~15ull; l.listB = l.listA + ((g * 4u + 15u) & ~15ull); l.total = l.listB + ((g * 4u + 15u) & ~15ull);
     return l;
-}
-// CLodPackViewPriority's quantisation (workGraphCulling.hlsl:1012-1018): round(clamp(errorOverDistance * 1024, 0, 65535)); NaN and negatives give 0
-__host__ __device__ inline uint32_t stream_priority16(float errorOverDistance) {
-    float c = errorOverDistance * 1024.0f;
-    c = c > 0.0f ? c : 0.0f;
-    c = c < 65535.0f ? c : 65535.0f;
-    return (uint32_t)(c + 0.5f);
 }
 
 // Scenes whose materials all pack to the same coat (fuzz) G-buffer word: the word and whether the plane currently holds it everywhere

@@ -89,7 +89,7 @@ def main():
                     continue
                 alloc = max(8, -(-(k["vgpr"] + k["agpr"]) // 8) * 8)
                 waves = min(8, 512 // alloc)
-                print(f"{name[:70]:70s} {k['vgpr']:5d} {k['agpr']:5d} {k['sgpr']:5d} {k['vspill']:6d} {k['sspill']:6d} {k['scratch']:7d} {k['lds']:7d} {waves:5d}")
+                print(f"{name:70s} {k['vgpr']:5d} {k['agpr']:5d} {k['sgpr']:5d} {k['vspill']:6d} {k['sspill']:6d} {k['scratch']:7d} {k['lds']:7d} {waves:5d}")
                 if k["scratch"]:
                     bad += 1
     if check and bad:
