@@ -229,7 +229,7 @@ BRMI_EXPORTS = ["brmi_abi_version", "brmi_default_config", "brmi_create", "brmi_
                 "brmi_update", "brmi_execute", "brmi_execute_split", "brmi_destroy", "brmi_last_error", "brmi_clear_visibility", "brmi_cull",
                 "brmi_raster", "brmi_depth_copy", "brmi_build_hzb", "brmi_invalidate_hzb", "brmi_set_history_source", "brmi_gbuffer", "brmi_light_clustering",
                 "brmi_shade", "brmi_set_shade_slabs", "brmi_read_counters", "brmi_stage_times", "brmi_set_timed_stages", "brmi_algorithmic_bytes", "brmi_algorithmic_bytes_launched", "brmi_debug_arith", "brmi_debug_arith_in_range", "brmi_debug_read_bin_records", "brmi_debug_wide_triangles", "brmi_debug_lean_clusters", "brmi_debug_read_lean_queue", "brmi_debug_read_held",
-                "brmi_streaming_scratch_bytes", "brmi_set_streaming", "brmi_streaming_feedback"]
+                "brmi_streaming_scratch_bytes", "brmi_set_streaming", "brmi_streaming_feedback", "brmi_set_sampler_anisotropy", "brmi_debug_sample_grad"]
 
 
 def brmi_lib():
@@ -276,5 +276,8 @@ def brmi_lib():
         lib.brmi_streaming_scratch_bytes.restype = u64
         lib.brmi_set_streaming.argtypes = [vp, C.POINTER(StreamingBuffers)]
         lib.brmi_streaming_feedback.argtypes = [vp, vp]
+        if hasattr(lib, "brmi_set_sampler_anisotropy"):      # (absent from an older build of the same ABI loaded through BRMI_LIB_PATH for an A/B run)
+            lib.brmi_set_sampler_anisotropy.argtypes = [vp, vp, u32]
+            lib.brmi_debug_sample_grad.argtypes = [C.POINTER(SceneBuffers), vp, u32, u32, u32, vp, vp, vp, vp, u32, vp]
         _brmi_lib = lib
     return _brmi_lib

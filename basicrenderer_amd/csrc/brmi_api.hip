@@ -310,6 +310,7 @@ int brmi_set_scene(brmi_pass* p, const brmi_scene_buffers* scene) {
     if (!p || !scene) return BRMI_ERR_INVALID;
     p->scene = *scene; p->haveScene = false; p->setupDone = false;
     p->streaming.on = false;      // (bound to the group table of the scene before: brmi_set_streaming again)
+    p->samplerAniso = nullptr;    // (one word per sampler of the scene before: brmi_set_sampler_anisotropy again)
     const brmi_scene_buffers& sc = p->scene;
     if (!sc.slabs || !sc.perObject || !sc.perMesh || !sc.perMeshInstance || !sc.clodOffsets || !sc.meshMetadata || !sc.lodNodes || !sc.lodGroups ||
         !sc.lodSegments || !sc.groupPageMap || !sc.materials || !sc.openpbrMaterials || !sc.cameras || !sc.cullingCameras || !sc.viewRasterInfo || !sc.perFrame ||
@@ -757,6 +758,14 @@ int brmi_set_streaming(brmi_pass* p, const brmi_streaming_buffers* b) {
     p->streaming.on = true;
     return BRMI_OK;
 }
+int brmi_set_sampler_anisotropy(brmi_pass* p, const uint32_t* maxAnisotropy, uint32_t count) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (!maxAnisotropy) { p->samplerAniso = nullptr; return BRMI_OK; }
+    if (!p->haveScene) return brmi::fail(p, BRMI_ERR_STATE, "brmi_set_sampler_anisotropy: brmi_set_scene first (the table has one word per sampler of the scene)");
+    if (count != p->scene.samplerCount) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_sampler_anisotropy: count %u, the scene has %u samplers", count, p->scene.samplerCount);
+    p->samplerAniso = maxAnisotropy;
+    return BRMI_OK;
+}
 int brmi_streaming_feedback(brmi_pass* p, brmi_stream stream) {
     CHECK_READY(p);
     if (!p->streaming.on) return brmi::fail(p, BRMI_ERR_STATE, "brmi_streaming_feedback: no streaming buffers bound (brmi_set_streaming)");
@@ -1087,6 +1096,13 @@ int brmi_debug_arith_in_range(const float* a, float* outRcp, float* outSqrt, flo
     if (n == 0) return BRMI_OK;
     hipLaunchKernelGGL(k_debug_arith_in_range, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), a, outRcp, outSqrt, outRsqrt, n);
     return hipGetLastError() == hipSuccess ? BRMI_OK : BRMI_ERR_HIP;
+}
+
+int brmi_debug_sample_grad(const brmi_scene_buffers* scene, const uint32_t* maxAnisotropy, uint32_t textureIndex, uint32_t samplerIndex, uint32_t uniformBinding, const float* uv, const float* ddx,
+                           const float* ddy, float* outRGBA, uint32_t n, brmi_stream stream) {
+    if (!scene || !uv || !ddx || !ddy || !outRGBA || (scene->textureCount && !scene->textures) || (scene->samplerCount && !scene->samplers)) return BRMI_ERR_INVALID;
+    if (n == 0) return BRMI_OK;
+    return brmi::launch_debug_sample_grad(*scene, maxAnisotropy, textureIndex, samplerIndex, uniformBinding != 0u, uv, ddx, ddy, outRGBA, n, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

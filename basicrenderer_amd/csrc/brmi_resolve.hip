@@ -38,6 +38,7 @@ struct GBufferArgs {
     uint32_t setupPart;            // k_resolve_setup: 0 = every visible cluster, 1 = the phase-1 clusters only (launched beside the rasteriser), 2 = the phase-2 clusters only
     uint32_t inlineRatio;          // a frame with more than 1 / inlineRatio cluster triangles per pixel resolves without the tables (resolve_inline_frame): what the kernels tell the host
     uint32_t variantSelect;        // 0: run; 1: run only when no cluster spilled out of the arena; 2: only when one did (counters[CNT_RESOLVE_SPILL])
+    const uint32_t* samplerAniso;  // brmi_set_sampler_anisotropy: maxAnisotropy per sampler, read by the ANISO instantiations alone (null: those are not launched)
 };
 
 BRMI_DEV f3 oct_decode_normal(uint32_t packed) {
@@ -281,13 +282,20 @@ constexpr int RESOLVE_WATERFALL = BRMI_RESOLVE_WATERFALL;     // distinct mesh i
 #ifndef BRMI_GBM_WAVES
 #define BRMI_GBM_WAVES 3
 #endif
+// the ANISO variants keep a tap loop's state (accumulator, major axis, the prepared level) over the fetches on top of the isotropic variants' registers:
+// 173 - 182 registers (214 - 227 with several UV sets) without spilling, where three or four waves per SIMD spilled 55 - 84 of them into scratch
+#ifndef BRMI_GBA_WAVES
+#define BRMI_GBA_WAVES 2
+#endif
 // Epi: what happens to a pixel's G-buffer words besides being stored.  `pixel()` is called once per lane and tile, in converged control flow,
 // after the tile's waterfall: nothing for the plain kernels (round 5 removed the fused G-buffer + shading kernel, which lost on measurement twice).
 struct NoEpilogue {
     static constexpr bool kWanted = false;
     BRMI_DEV void pixel(bool, unsigned long long, bool, uint32_t, uint32_t, uint64_t, const float4&, uint32_t, uint32_t, unsigned long long, unsigned long long) const {}
 };
-template <bool INLINE_TABLES, bool TEXTURED, bool PARALLAX, bool MULTI_UV, int SLIM, class Epi>
+// ANISO: a per-sampler maxAnisotropy table is bound (brmi_set_sampler_anisotropy): the material slots' SampleGrad is sample_grad_aniso.  Instantiations of
+// their own, so that frames without a table launch the code they always did; the parallax march's height fetches stay isotropic in both.
+template <bool INLINE_TABLES, bool TEXTURED, bool PARALLAX, bool MULTI_UV, int SLIM, bool ANISO, class Epi>
 BRMI_DEV void gbuffer_body(const GBufferArgs& a, const Epi& epi) {
     const brmi_scene_buffers& sc = a.sc;
     if (a.variantSelect != 0u && (a.counters[CNT_RESOLVE_SPILL] != 0u) != (a.variantSelect == 2u)) return;     // the other variant's frame
@@ -436,7 +444,11 @@ BRMI_DEV void gbuffer_body(const GBufferArgs& a, const Epi& epi) {
                     interpolate(tc);
                     // texture / sampler tables in the address space of the material pointer: scalar loads on the waterfall path
                     auto texturesP = as_space_of(mat, sc.textures); auto samplersP = as_space_of(mat, sc.samplers);
-                    auto bind = [&](uint32_t ti, uint32_t si) { return bind_texture(texturesP, sc.textureCount, samplersP, sc.samplerCount, ti, si); };
+                    auto bind = [&](uint32_t ti, uint32_t si) {
+                        if constexpr (ANISO) return bind_texture(texturesP, sc.textureCount, samplersP, sc.samplerCount, ti, si, as_space_of(mat, a.samplerAniso));
+                        else return bind_texture(texturesP, sc.textureCount, samplersP, sc.samplerCount, ti, si);
+                    };
+                    auto sample = [&](const TexBinding& b) { return ANISO ? sample_grad_aniso(tb, b, uv, dUVdx, dUVdy) : sample_grad(tb, b, uv, dUVdx, dUVdy); };
                     f3 Tn{}, Bn{};
                     auto cotangent_frame = [&]() {
                         // dpdx / dpdy through the model's 3x3 (clodResolveCommon.hlsli:1607-1624), cotangent_frame_from_derivs (utilities.hlsli:323-336)
@@ -483,7 +495,7 @@ BRMI_DEV void gbuffer_body(const GBufferArgs& a, const Epi& epi) {
                             if (!(flags & bit)) continue;
                             use_set(set);
                             f4 t = prevSample;
-                            if (ti != prevTi || si != prevSi || (MULTI_UV && curSet != prevSet) || ti >= sc.textureCount || si >= sc.samplerCount) t = sample_grad(tb, bind(ti, si), uv, dUVdx, dUVdy);
+                            if (ti != prevTi || si != prevSi || (MULTI_UV && curSet != prevSet) || ti >= sc.textureCount || si >= sc.samplerCount) t = sample(bind(ti, si));
                             prevTi = ti; prevSi = si; prevSet = curSet; prevSample = t;
                             if (slot == 0u) baseColor = f4{baseColor.x * t.x, baseColor.y * t.y, baseColor.z * t.z, baseColor.w * t.w};
                             else if (slot == 1u) metallic = swizzle4(t, mat->metallicChannel) * mat->metallicFactor;
@@ -525,7 +537,7 @@ BRMI_DEV void gbuffer_body(const GBufferArgs& a, const Epi& epi) {
                                 if (ti == 0xFFFFFFFFu || si == 0xFFFFFFFFu) continue;
                                 use_set(set);
                                 f4 t = prevSample;
-                                if (ti != prevTi || si != prevSi || (MULTI_UV && curSet != prevSet) || ti >= sc.textureCount || si >= sc.samplerCount) t = sample_grad(tb, bind(ti, si), uv, dUVdx, dUVdy);
+                                if (ti != prevTi || si != prevSi || (MULTI_UV && curSet != prevSet) || ti >= sc.textureCount || si >= sc.samplerCount) t = sample(bind(ti, si));
                                 prevTi = ti; prevSi = si; prevSet = curSet; prevSample = t;
                                 if (slot == 0u) cc = sat3(coatColor * f3{swizzle4(t, tbw(12)), swizzle4(t, tbw(13)), swizzle4(t, tbw(14))});
                                 else if (slot == 1u) cw = sat(sat(opRec->coatWeight) * swizzle4(t, tbw(16)));
@@ -576,12 +588,17 @@ BRMI_DEV void gbuffer_body(const GBufferArgs& a, const Epi& epi) {
 }
 template <bool INLINE_TABLES, bool TEXTURED, bool PARALLAX = false, bool MULTI_UV = false, int SLIM = 0>
 __global__ void __launch_bounds__(256, INLINE_TABLES ? 1 : (MULTI_UV ? (PARALLAX ? BRMI_GBPM_WAVES : BRMI_GBM_WAVES) : (PARALLAX ? BRMI_GBP_WAVES : (TEXTURED ? BRMI_GBT_WAVES : BRMI_GB_WAVES)))) k_gbuffer(GBufferArgs a) {
-    gbuffer_body<INLINE_TABLES, TEXTURED, PARALLAX, MULTI_UV, SLIM>(a, NoEpilogue{});
+    gbuffer_body<INLINE_TABLES, TEXTURED, PARALLAX, MULTI_UV, SLIM, false>(a, NoEpilogue{});
+}
+// the ANISO = true instantiations of the textured body under a name of their own: k_gbuffer's instantiations keep the names (and the code) they had
+template <bool INLINE_TABLES, bool PARALLAX = false, bool MULTI_UV = false, int SLIM = 0>
+__global__ void __launch_bounds__(256, INLINE_TABLES ? 1 : BRMI_GBA_WAVES) k_gbuffer_aniso(GBufferArgs a) {
+    gbuffer_body<INLINE_TABLES, true, PARALLAX, MULTI_UV, SLIM, true>(a, NoEpilogue{});
 }
 
 static GBufferArgs gbuffer_args_of(brmi_pass* p) {
     GBufferArgs a;
-    a.hostFeedback = nullptr; a.setupPart = 0u; a.inlineRatio = resolve_inline_ratio(p);
+    a.hostFeedback = nullptr; a.setupPart = 0u; a.inlineRatio = resolve_inline_ratio(p); a.samplerAniso = p->samplerAniso;
     a.sc = shading_scene_of(p);      // the frame's camera / per-frame record as the constants kernel saw them (FrameSnapshot)
     a.clusters = static_cast<const uint4*>(p->res[BRMI_RES_VISIBLE_CLUSTERS]); a.counters = p->counters();
     a.vis = static_cast<const unsigned long long*>(p->res[BRMI_RES_VISIBILITY]);
@@ -664,15 +681,56 @@ int launch_gbuffer(brmi_pass* p, hipStream_t s) {
         // (SLIM: 0 / 1 / 2 as decided above)
 #define BRMI_GB_LAUNCH(T, P, M) do { if (slim == 2) launch(k_gbuffer<false, T, P, M, 2>, k_gbuffer<true, T, P, M>); else if (slim == 1) launch(k_gbuffer<false, T, P, M, 1>, k_gbuffer<true, T, P, M>); \
                                      else launch(k_gbuffer<false, T, P, M>, k_gbuffer<true, T, P, M>); } while (0)
-        if (p->sceneHasParallax) { if (multiUv) BRMI_GB_LAUNCH(true, true, true); else BRMI_GB_LAUNCH(true, true, false); }      // its own variants: the ray march costs the others registers they would spill
+#define BRMI_GBA_LAUNCH(P, M) do { if (slim == 2) launch(k_gbuffer_aniso<false, P, M, 2>, k_gbuffer_aniso<true, P, M>); else if (slim == 1) launch(k_gbuffer_aniso<false, P, M, 1>, k_gbuffer_aniso<true, P, M>); \
+                                   else launch(k_gbuffer_aniso<false, P, M>, k_gbuffer_aniso<true, P, M>); } while (0)
+        // a bound maxAnisotropy table (brmi_set_sampler_anisotropy) selects the ANISO instantiations; without one the launches are the ones they always were
+        if (p->samplerAniso && p->sceneHasTextures) {
+            if (p->sceneHasParallax) { if (multiUv) BRMI_GBA_LAUNCH(true, true); else BRMI_GBA_LAUNCH(true, false); }
+            else if (multiUv) BRMI_GBA_LAUNCH(false, true);
+            else BRMI_GBA_LAUNCH(false, false);
+        } else if (p->sceneHasParallax) { if (multiUv) BRMI_GB_LAUNCH(true, true, true); else BRMI_GB_LAUNCH(true, true, false); }      // its own variants: the ray march costs the others registers they would spill
         else if (multiUv) BRMI_GB_LAUNCH(true, false, true);
         else BRMI_GB_LAUNCH(true, false, false);
     } else if (p->inlineResolve && slim == 2) launch(k_gbuffer<false, false, false, false, 2>, k_gbuffer<true, false, false, false, 2>);      // (the in-place form of scenes without textures has the slim instantiations too)
     else if (p->inlineResolve && slim == 1) launch(k_gbuffer<false, false, false, false, 1>, k_gbuffer<true, false, false, false, 1>);
     else BRMI_GB_LAUNCH(false, false, false);
 #undef BRMI_GB_LAUNCH
+#undef BRMI_GBA_LAUNCH
     BRMI_LAUNCH_CHECK(p, "k_gbuffer");
     return BRMI_OK;
+}
+
+// brmi_debug_sample_grad: the sampler as the G-buffer kernel calls it, one lane per sample.  UNIFORM: the descriptors come through the constant address
+// space as on the kernel's waterfall path (the power-of-two fast path is reachable); otherwise every lane binds for itself (the general path).
+template <bool UNIFORM>
+__global__ void __launch_bounds__(256) k_debug_sample_grad(const brmi_texture_desc* textures, uint32_t textureCount, const brmi_sampler_desc* samplers, uint32_t samplerCount, const float* srgbToLinear,
+                                                           const uint32_t* maxAnisotropy, uint32_t textureIndex, uint32_t samplerIndex, const float2* uv, const float2* ddx, const float2* ddy, float4* out, uint32_t n) {
+    __shared__ float texelTables[512];
+    stage_texel_tables(texelTables, srgbToLinear, threadIdx.x, 256u); __syncthreads();
+    TexelTables tb; tb.t = texelTables;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f2 u{uv[i].x, uv[i].y}, dx{ddx[i].x, ddx[i].y}, dy{ddy[i].x, ddy[i].y};
+    f4 r;
+    if (maxAnisotropy) {
+        const TexBinding b = UNIFORM ? bind_texture(kconst(textures), textureCount, kconst(samplers), samplerCount, textureIndex, samplerIndex, kconst(maxAnisotropy))
+                                     : bind_texture(textures, textureCount, samplers, samplerCount, textureIndex, samplerIndex, maxAnisotropy);
+        r = sample_grad_aniso(tb, b, u, dx, dy);
+    } else {
+        const TexBinding b = UNIFORM ? bind_texture(kconst(textures), textureCount, kconst(samplers), samplerCount, textureIndex, samplerIndex)
+                                     : bind_texture(textures, textureCount, samplers, samplerCount, textureIndex, samplerIndex);
+        r = sample_grad(tb, b, u, dx, dy);
+    }
+    out[i] = make_float4(r.x, r.y, r.z, r.w);
+}
+int launch_debug_sample_grad(const brmi_scene_buffers& sc, const uint32_t* maxAnisotropy, uint32_t textureIndex, uint32_t samplerIndex, bool uniformBinding, const float* uv, const float* ddx, const float* ddy,
+                             float* outRGBA, uint32_t n, hipStream_t s) {
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, sc.textures, sc.textureCount, sc.samplers, sc.samplerCount, sc.srgbToLinear, maxAnisotropy, textureIndex, samplerIndex,
+                           reinterpret_cast<const float2*>(uv), reinterpret_cast<const float2*>(ddx), reinterpret_cast<const float2*>(ddy), reinterpret_cast<float4*>(outRGBA), n);
+    };
+    if (uniformBinding) launch(k_debug_sample_grad<true>); else launch(k_debug_sample_grad<false>);
+    return hipGetLastError() == hipSuccess ? BRMI_OK : BRMI_ERR_HIP;
 }
 
 }  // namespace brmi

@@ -10,7 +10,10 @@
 //   addressing on integer texel coordinates (wrap, mirror, clamp); point = floor(u * w); linear = the 2x2 footprint around
 //   u * w - 0.5 blended a + t * (b - a) along x then y; SampleGrad's lod = 0.5 * log2(max(|ddx * size|^2, |ddy * size|^2)) with
 //   log2 = exponent + degree-5 mantissa polynomial; lod biased, clamped to the sampler's range and the mip chain; lod <= 0 takes
-//   the mag filter; mip filter point = nearest level, linear = two levels blended by the fraction.  Anisotropy is not reproduced.
+//   the mag filter; mip filter point = nearest level, linear = two levels blended by the fraction.
+// Anisotropic filtering (sample_grad_aniso) is the project's own definition in the shape of EXT_texture_filter_anisotropic: up to
+// maxAnisotropy SampleLevel taps along the footprint's major axis at the level of its minor axis.  It is off unless a per-sampler maxAnisotropy table is
+// bound (brmi_set_sampler_anisotropy); the parallax march's height fetches and the rasteriser's alpha test stay isotropic.
 #ifndef BRMI_TEXTURE_H
 #define BRMI_TEXTURE_H
 
@@ -84,7 +87,8 @@ BRMI_DEV void stage_texel_tables(float* lds512, const float* srgbToLinear, uint3
 // one texture slot as the sampler sees it: descriptor and sampler state, fetched once per material (scalar loads when the
 // material index is wave-uniform: pass the tables through kconst())
 struct TexBinding { const uint32_t* texels; const uint32_t* mipOffset; uint32_t width, height, mipCount; bool srgb, bound; brmi_sampler_desc sm;
-                    bool waveUniform; };      // the descriptors came through the constant address space (scalar loads): every field is the same in all lanes
+                    bool waveUniform;         // the descriptors came through the constant address space (scalar loads): every field is the same in all lanes
+                    uint32_t aniso; };        // the sampler's maxAnisotropy clamped to [1, 16] (0: no table bound; reads as 1), consumed by sample_grad_aniso alone
 template <typename T> struct is_kconst_ptr { static constexpr bool value = false; };
 template <typename T> struct is_kconst_ptr<const __attribute__((address_space(4))) T*> { static constexpr bool value = true; };
 template <typename TexPtr, typename SampPtr>
@@ -99,6 +103,13 @@ BRMI_DEV TexBinding bind_texture(TexPtr textures, uint32_t textureCount, SampPtr
     b.width = td->width; b.height = td->height; b.mipCount = td->mipCount; b.srgb = td->format == BRMI_TEXTURE_FORMAT_RGBA8_UNORM_SRGB;
     b.sm.addressU = sd->addressU; b.sm.addressV = sd->addressV; b.sm.minFilter = sd->minFilter; b.sm.magFilter = sd->magFilter; b.sm.mipFilter = sd->mipFilter;
     b.sm.mipLodBias = sd->mipLodBias; b.sm.minLod = sd->minLod; b.sm.maxLod = sd->maxLod;
+    return b;
+}
+// ... with the sampler's word of the per-sampler maxAnisotropy table (brmi_set_sampler_anisotropy), in the address space of the descriptors
+template <typename TexPtr, typename SampPtr, typename AnisoPtr>
+BRMI_DEV TexBinding bind_texture(TexPtr textures, uint32_t textureCount, SampPtr samplers, uint32_t samplerCount, uint32_t textureIndex, uint32_t samplerIndex, AnisoPtr maxAnisotropy) {
+    TexBinding b = bind_texture(textures, textureCount, samplers, samplerCount, textureIndex, samplerIndex);
+    if (b.bound) { const uint32_t v = maxAnisotropy[samplerIndex]; b.aniso = v < 1u ? 1u : (v > 16u ? 16u : v); }
     return b;
 }
 BRMI_DEV bool same_binding(const TexBinding& a, const TexBinding& b) {
@@ -240,6 +251,59 @@ BRMI_DEV float grad_lod(const TexBinding& tx, f2 dUVdx, f2 dUVdy) {
 BRMI_DEV f4 sample_grad(const TexelTables& tb, const TexBinding& tx, f2 uv, f2 dUVdx, f2 dUVdy) {
     if (!tx.bound) return {1.0f, 1.0f, 1.0f, 1.0f};
     return sample_level(tb, tx, uv, grad_lod(tx, dUVdx, dUVdy));
+}
+
+// Anisotropic SampleGrad.  The decision -- squared axis lengths, the tap count N, the level of detail -- needs neither a square root nor a
+// division, so host and device decide alike.  N = the smallest n in [1, A] with n^2 * minor2 >= major2 (A if none): n^2 * minor2 grows with n, so N is one
+// more than the number of n < A that fail the comparison -- fifteen multiply-compare pairs, no loop.  A lane with N == 1 (A == 1, a square footprint, a
+// NaN or out-of-range axis) computes today's sample_grad: grad_lod's level, the texcoord itself, a sum of one tap times 1.0f.
+// The taps run in a loop to the wave's largest N with the lanes past their own N masked; what depends on the level alone (prepare_level: both mip offsets
+// requested together; the Pow2Axis constants; whether any lane blends two levels) is settled once in front of it, and each tap keeps sample_prepared's
+// memory shape: both footprints requested, then filtered.  A wave whose lanes all have N == 1 takes sample_grad itself and never enters the loop.
+template <bool POW2>
+BRMI_DEV f4 sample_tap(const TexelTables& tb, const TexBinding& tx, const Pow2Axis& ax, const Pow2Axis& ay, const LevelSetup& s, bool blend, f2 uv) {
+    const Footprint f0 = POW2 ? fetch_footprint_pow2(tx, ax, ay, s.off0, s.l0, uv) : fetch_footprint(tx, s.off0, s.l0, uv, s.filter);
+    if (!blend) return filter_footprint(tb, f0, tx.srgb);
+    const Footprint f1 = POW2 ? fetch_footprint_pow2(tx, ax, ay, s.off1, s.l1, uv) : fetch_footprint(tx, s.off1, s.l1, uv, s.filter);
+    const f4 a = filter_footprint(tb, f0, tx.srgb);
+    return s.frac == 0.0f ? a : lerp4(a, filter_footprint(tb, f1, tx.srgb), s.frac);
+}
+template <bool POW2>
+BRMI_DEV f4 sample_taps(const TexelTables& tb, const TexBinding& tx, const LevelSetup& s, f2 uv, f2 major, uint32_t N) {
+    const Pow2Axis ax = POW2 ? pow2_axis(tx.width, tx.sm.addressU) : Pow2Axis{}, ay = POW2 ? pow2_axis(tx.height, tx.sm.addressV) : Pow2Axis{};
+    const bool blend = __any(s.frac != 0.0f);
+    const float fN = (float)N;
+    f4 acc{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma nounroll
+    for (uint32_t i = 0; __any(i < N); i++) {
+        if (i < N) {
+            const float t = ((float)i + 0.5f) / fN - 0.5f;
+            const f2 uvi = N > 1u ? f2{uv.x + major.x * t, uv.y + major.y * t} : uv;
+            const f4 tap = sample_tap<POW2>(tb, tx, ax, ay, s, blend, uvi);
+            acc = i == 0u ? tap : f4{acc.x + tap.x, acc.y + tap.y, acc.z + tap.z, acc.w + tap.w};
+        }
+    }
+    const float inv = 1.0f / fN;
+    return {acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv};
+}
+BRMI_DEV f4 sample_grad_aniso(const TexelTables& tb, const TexBinding& tx, f2 uv, f2 dUVdx, f2 dUVdy) {
+    if (!tx.bound) return {1.0f, 1.0f, 1.0f, 1.0f};
+    const float W = (float)tx.width, H = (float)tx.height;
+    const float dxx = dUVdx.x * W, dxy = dUVdx.y * H, dyx = dUVdy.x * W, dyy = dUVdy.y * H;
+    const float lx2 = dxx * dxx + dxy * dxy, ly2 = dyx * dyx + dyy * dyy;
+    const float major2 = max2(lx2, ly2), minor2 = min2(lx2, ly2);
+    const uint32_t A = tx.aniso;
+    uint32_t N = 1u;
+    if (A > 1u && lx2 == lx2 && ly2 == ly2 && major2 >= 1.17549435e-38f && major2 <= 3.0e38f) {
+#pragma unroll
+        for (uint32_t n = 1u; n < 16u; n++) N += (n < A && !((float)(n * n) * minor2 >= major2)) ? 1u : 0u;
+    }
+    if (!__any(N > 1u)) return sample_grad(tb, tx, uv, dUVdx, dUVdy);
+    const float lod = N > 1u ? 0.5f * log2_poly(major2) - log2_poly((float)N) : grad_lod(tx, dUVdx, dUVdy);
+    const f2 major = lx2 >= ly2 ? dUVdx : dUVdy;
+    const LevelSetup s = prepare_level(tx, lod);
+    if (pow2_fast_path(tx)) return sample_taps<true>(tb, tx, s, uv, major, N);      // (a scalar branch; not compiled at all for per-lane bindings)
+    return sample_taps<false>(tb, tx, s, uv, major, N);
 }
 
 // SWAlphaTestFailed (CLOD_SW_RASTER_DYNAMIC_ALPHA_TEST).  Everything that depends on the material alone -- the two texture

@@ -88,7 +88,8 @@ protected:
     std::string name_;
 };
 
-#define BRMI_STAGE_PASS(CLASS, NAME, CALL, SRVS, UAVS)                                                        \
+#define BRMI_STAGE_PASS(CLASS, NAME, CALL, SRVS, UAVS) BRMI_STAGE_PASS_WITH(CLASS, NAME, CALL, SRVS, UAVS, )
+#define BRMI_STAGE_PASS_WITH(CLASS, NAME, CALL, SRVS, UAVS, MEMBERS)                                          \
     class CLASS final : public ComputePass {                                                                  \
     public:                                                                                                   \
         explicit CLASS(std::shared_ptr<PassState> st) : ComputePass(std::move(st), NAME) {}                   \
@@ -99,6 +100,7 @@ protected:
             b->WithIndirectArguments("brmi::Workspace");   /* cluster / record counts read on the device */   \
         }                                                                                                     \
         PassReturn Execute(PassExecutionContext& ctx) override { state->check(CALL, NAME); return {}; }       \
+        MEMBERS                                                                                               \
     };
 
 // reference: ClearVisibilityBufferPass (BR/include/RenderPasses/ClearVisibilityBufferPass.h)
@@ -130,11 +132,14 @@ BRMI_STAGE_PASS(SoftwareRasterizeClustersPass2, "SoftwareRasterizeClustersPass2"
                   "Builtin::PerMaterialDataBuffer", "material textures + samplers (alpha test)"}),
                 ({"Builtin::PrimaryCamera::VisibilityTexture"}))
 // reference: MaterialHistogram .. EvaluateMaterialGroups (BR/include/RenderPasses/VisUtil/*.h; parameter list at EvaluateMaterialGroupsPass.h:68-111)
-BRMI_STAGE_PASS(EvaluateMaterialGroupsPass, "EvaluateMaterialGroupsPass", brmi_gbuffer(state->get(), ctx.commandList),
+// SetSamplerAnisotropy: rhi::SamplerDesc::maxAnisotropy of the scene's samplers, one DEVICE word each, graph-owned (nullptr: isotropic, the default); call it after
+// PassState::SetScene, which forgets the table (brmi_set_sampler_anisotropy)
+BRMI_STAGE_PASS_WITH(EvaluateMaterialGroupsPass, "EvaluateMaterialGroupsPass", brmi_gbuffer(state->get(), ctx.commandList),
                 ({"Builtin::PrimaryCamera::VisibilityTexture", "Builtin::CLod::VisibleClusters", "Builtin::PerMaterialDataBuffer", "Builtin::PerMaterialOpenPBRDataBuffer",
                   "Builtin::NormalMatrixBuffer", "CLod page slabs", "material textures + samplers"}),
                 ({"Builtin::GBuffer::Normals", "Builtin::GBuffer::Albedo", "Builtin::GBuffer::Coat", "Builtin::GBuffer::Emissive", "Builtin::GBuffer::Fuzz",
-                  "Builtin::GBuffer::MetallicRoughness", "Builtin::GBuffer::MotionVectors", "Builtin::PrimaryCamera::LinearDepthMap"}))
+                  "Builtin::GBuffer::MetallicRoughness", "Builtin::GBuffer::MotionVectors", "Builtin::PrimaryCamera::LinearDepthMap"}),
+                void SetSamplerAnisotropy(const uint32_t* maxAnisotropy, uint32_t count) { state->check(brmi_set_sampler_anisotropy(state->get(), maxAnisotropy, count), "brmi_set_sampler_anisotropy"); })
 // reference: ClusterGenerationPass + LightCullingPass (BR/include/RenderPasses/ClusterGenerationPass.h:41-42, LightCullingPass.h:49-51)
 BRMI_STAGE_PASS(LightCullingPass, "LightCullingPass", brmi_light_clustering(state->get(), ctx.commandList),
                 ({"Builtin::Light::InfoBuffer", "Builtin::Light::ActiveLightIndices", "Builtin::CameraBuffer"}),
@@ -146,6 +151,7 @@ BRMI_STAGE_PASS(DeferredShadingPass, "DeferredShadingPass", brmi_shade(state->ge
                   "Builtin::OpenPBR::*"}),
                 ({"Builtin::Color::HDRColorTarget"}))
 #undef BRMI_STAGE_PASS
+#undef BRMI_STAGE_PASS_WITH
 
 // ---- the extension interface (BR/include/Render/GraphExtensions/CLodExtension.h:20-31) ------------------------------------------
 // Stand-ins for the graph-side types the five hooks take (OpenRenderGraph is an empty submodule in the reference checkout).

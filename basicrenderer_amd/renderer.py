@@ -75,6 +75,7 @@ class VisibilityRenderer:
         self.sb, self._scene_keep = scene.device_buffers(self.device)
         self.device_arrays = dict(scene.device_arrays)      # this pass's own copies (two passes in flight each have their camera buffers)
         self._check(self.lib.brmi_set_scene(self._h, C.byref(self.sb)), "brmi_set_scene")
+        self._anisotropy = None      # set_anisotropy's table
         self.descs = {}
 
         def cb(_user, d):
@@ -330,6 +331,26 @@ class VisibilityRenderer:
         self.torch.cuda.synchronize(self.device)
         r, t, c = self.streaming_tensors()
         return self.unpack_feedback(r.cpu().numpy(), t.cpu().numpy(), c.cpu().numpy())
+
+    # -- anisotropic filtering (brmi_set_sampler_anisotropy) ---------------------------------------
+    def set_anisotropy(self, values):
+        """maxAnisotropy of the scene's samplers from the next frame on: an int for every sampler, a sequence with one entry per sampler, or None for
+        off (the isotropic sampler, exactly the frames of a pass that never called this).  Values are clamped to [1, 16] by the sampler; 0 reads as 1.
+        The table is this pass's own tensor; replacing or dropping one waits for the device first, since a frame still in flight (on whichever stream its
+        G-buffer half runs) may be reading it."""
+        if self._anisotropy is not None:
+            self.torch.cuda.synchronize(self.device)
+        if values is None:
+            self._check(self.lib.brmi_set_sampler_anisotropy(self._h, None, capi.u32(0)), "brmi_set_sampler_anisotropy")
+            self._anisotropy = None
+            return
+        count = int(self.sb.samplerCount)
+        words = np.full(count, int(values), dtype=np.uint32) if np.isscalar(values) else np.ascontiguousarray(values, dtype=np.uint32).reshape(-1)
+        if len(words) != count:
+            raise BrmiError(f"set_anisotropy: {len(words)} values for the scene's {count} samplers")
+        table = self.torch.from_numpy(np.concatenate([words, np.zeros(1, dtype=np.uint32)]).view(np.int32)).to(self.device)      # (never empty)
+        self._check(self.lib.brmi_set_sampler_anisotropy(self._h, table.data_ptr(), capi.u32(count)), "brmi_set_sampler_anisotropy")
+        self._anisotropy = table
 
     def set_history_source(self, other):
         """Frames in flight: phase 1 tests against the depth chain `other` built for the frame before (None unlinks)."""

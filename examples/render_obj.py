@@ -30,6 +30,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("obj"); ap.add_argument("png")
     ap.add_argument("--size", default="1920x1080"); ap.add_argument("--lights", type=int, default=32); ap.add_argument("--features", type=int, default=0)
+    ap.add_argument("--anisotropy", type=int, default=0, metavar="N", help="maxAnisotropy of every sampler, 1..16 (default: off, the isotropic sampler)")
     a = ap.parse_args()
     from basicrenderer_amd import Scene
     from basicrenderer_amd.obj import frame_view, load_obj
@@ -44,6 +45,8 @@ def main():
         instances, view = [(k, np.eye(4, dtype=np.float32)) for k in range(len(meshes))], frame_view(meshes)
     sc = Scene(width=w, height=h, point_lights=a.lights, material_features=a.features, meshes=meshes, instances=instances, view=view)
     r = VisibilityRenderer(sc, occlusion=True)
+    if a.anisotropy > 0:
+        r.set_anisotropy(a.anisotropy)
     r.execute(); r.execute()
     hdr = r.hdr().view(np.float16).reshape(h, w, 4)[..., :3].astype(np.float32)
     ldr = hdr / (1.0 + hdr)

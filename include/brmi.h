@@ -240,6 +240,12 @@ const char* brmi_last_error(const brmi_pass* pass);
 uint64_t brmi_streaming_scratch_bytes(uint32_t lodGroupCount);
 int brmi_set_streaming(brmi_pass* pass, const brmi_streaming_buffers* streaming);
 
+/* Per-sampler maxAnisotropy for the G-buffer pass's SampleGrad (up to maxAnisotropy SampleLevel taps along the footprint's major axis; a word is
+ * clamped to [1, 16], 0 reads as 1; the parallax march's height fetches and the rasteriser's alpha test stay isotropic).  `maxAnisotropy`: DEVICE pointer to
+ * samplerCount words, caller-owned, read by the frame's G-buffer launch.  NULL switches it off and gives exactly the frames of a pass that never called it.
+ * Call after brmi_set_scene (which forgets the binding).  BRMI_ERR_INVALID: count != the scene's samplerCount. */
+int brmi_set_sampler_anisotropy(brmi_pass* pass, const uint32_t* maxAnisotropy, uint32_t count);
+
 /* Rows [bandY0, bandY1) of the frame this GPU renders FROM THE NEXT FRAME ON (multiples of 8; passes created with brmi_config::dynamicBand): call it between frames,
  * before the frame's brmi_update.  The screen-tile split of SURVEY.md 8(e) with regions whose boundaries follow the cost of the frames before, so that every GPU takes
  * the same time: a cluster is set up by the one GPU whose band holds it (two at a boundary), and the band test of the instance / node / cluster culling drops the rest
@@ -325,6 +331,16 @@ int brmi_debug_read_bin_records(brmi_pass* pass, void* dst, uint64_t bytes);
 /* The shading pass's in-range forms of 1 / a, sqrt(a) and 1 / sqrt(a) (brmi_device.h: the IEEE expansions without their scaling prologue and
  * fix-up epilogue for 2^-63 <= a < 2^63, the general form elsewhere): a test compares them bit for bit with the host's IEEE results. */
 int brmi_debug_arith_in_range(const float* a, float* outRcp, float* outSqrt, float* outRsqrt, uint32_t n, brmi_stream stream);
+
+
+/* The G-buffer pass's SampleGrad on device data, one lane per sample, through the very device function the kernel calls (the texel tables staged in LDS as
+ * there): a test compares it bit for bit with the host's statement of the sampler.  Of `scene` only textures / samplers / their counts / srgbToLinear are
+ * read.  maxAnisotropy: the table of brmi_set_sampler_anisotropy (samplerCount words), or NULL for the isotropic SampleGrad.  uniformBinding = 1 fetches the
+ * descriptors through the constant address space as the kernel's waterfall path does (the power-of-two fast path is reachable), 0 binds per lane (the
+ * general path).  uv / ddx / ddy: n float2 each; outRGBA: n float4.  Every pointer is a device pointer. */
+int brmi_debug_sample_grad(const brmi_scene_buffers* scene, const uint32_t* maxAnisotropy /* device, or NULL */, uint32_t textureIndex,
+                           uint32_t samplerIndex, uint32_t uniformBinding, const float* uv, const float* ddx, const float* ddy, float* outRGBA,
+                           uint32_t n, brmi_stream stream);
 
 #ifdef __cplusplus
 }

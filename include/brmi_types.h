@@ -399,7 +399,9 @@ typedef struct brmi_openpbr_material_info {
  * brmi_scene_buffers::textures, `*SamplerIndex` indexes brmi_scene_buffers::samplers.  Texels are RGBA8, row-major,
  * the mip chain tightly packed (level l starts mipOffset[l] texels after `texels`, size max(1, w >> l) x max(1, h >> l)).
  * The sampler is evaluated in software (DESIGN.md "software sampler"): rhi::SamplerDesc fields of
- * BR/src/Resources/Sampler.cpp:20-40 / BR/src/Import/GlTFLoader.cpp:856-885 that an isotropic filter reads. */
+ * BR/src/Resources/Sampler.cpp:20-40 / BR/src/Import/GlTFLoader.cpp:856-885 that an isotropic filter reads.  rhi::SamplerDesc::maxAnisotropy is
+ * not a field of brmi_sampler_desc (its 32 bytes are read as they are by every fixture): it travels in a table of its own, one word per sampler,
+ * bound with brmi_set_sampler_anisotropy; without the table every sampler filters isotropically. */
 #define BRMI_TEXTURE_FORMAT_RGBA8_UNORM       0u
 #define BRMI_TEXTURE_FORMAT_RGBA8_UNORM_SRGB  1u     /* rgb decoded through brmi_scene_buffers::srgbToLinear before filtering */
 #define BRMI_TEXTURE_MAX_MIPS                 16u
