@@ -58,59 +58,83 @@ BRMI_DEV f3 oct_decode_normal(uint32_t packed) {
 // derives from the triangle alone -- the three projected vertices, 1/w, the screen-space derivatives of the barycentrics --
 // and the decoded vertex normals are evaluated once per triangle / vertex here with the shader's operation order; the pixel
 // pass then only evaluates the part that depends on the pixel.  (The reference shader recomputes all of it per pixel.)
+// (the tables of cluster `c` by the calling wave; cx / cy / cw: its LDS, BRMI_MESHLET_MAX_VERTS floats each)
+BRMI_DEV void resolve_setup_cluster(const GBufferArgs& a, uint32_t c, uint32_t lane, float* cx, float* cy, float* cw) {
+    const ClusterSetup cs = a.setup[c];
+    if (cs.vertBase == BRMI_ARENA_NONE) return;           // arena full: the pixel pass walks this cluster's data itself
+    const uint32_t vertCount = cs.counts & 0xFFu, triCount = (cs.counts >> 8) & 0xFFu, posFormat = (cs.counts >> 16) & 0xFFu;
+    const m4 objectToClip = load_m4(a.objConst + (size_t)cs.perObjectIndex * OBJ_CONST_FLOATS + 16u);
+    const bool skinned = (cs.counts & BRMI_CS_SKINNED) != 0u;
+    const uint32_t skinSlot = skinned ? a.sc.perMeshInstance[cs.instanceIndex].skinningInstanceSlot : 0xFFFFFFFFu;
+    for (uint32_t v = lane; v < vertCount; v += 64) {
+        f3 p{0.0f, 0.0f, 0.0f};
+        if (posFormat == BRMI_POSITION_FORMAT_FLOAT3) { const float* pp = reinterpret_cast<const float*>(cs.posBase + v * 12u); p = f3{pp[0], pp[1], pp[2]}; }
+        f3 n = oct_decode_normal(*reinterpret_cast<const uint32_t*>(cs.nrmBase + v * 4u));
+        if (skinned) {      // ApplyClodSkinning (clodResolveCommon.hlsli:702-714): once per vertex here, not once per pixel and corner
+            uint32_t joints[8]; float weights[8];
+            load_skin_influences((cs.counts & BRMI_CS_JOINTS) ? cs.nrmBase + cs.jointDelta + v * 32u : nullptr, (cs.counts & BRMI_CS_WEIGHTS) ? cs.nrmBase + cs.weightDelta + v * 32u : nullptr, joints, weights);
+            const m4 skin = build_skin_matrix(a.sc.skinningMatrices, skinSlot, joints, weights);
+            p = xyz(mul_point(p, skin)); n = mul_v3m3(n, skin);
+        }
+        const f4 clip = mul_point(p, objectToClip);
+        cx[v] = clip.x; cy[v] = clip.y; cw[v] = clip.w;
+        a.verts[cs.vertBase + v] = ResolveVertex{p.x, p.y, p.z, n.x, n.y, n.z};
+        if (a.uvs && (cs.counts & BRMI_CS_TEXTURED))
+            for (uint32_t set = 0; set < a.uvSets; set++) { const f2 uv = decode_uv_set(a.clusterUv[c], set, v); a.uvs[(size_t)set * a.vertCapacity + cs.vertBase + v] = make_float2(uv.x, uv.y); }
+        if (a.colors && (cs.counts & BRMI_CS_COLOR)) a.colors[cs.vertBase + v] = reinterpret_cast<const uint32_t*>(a.clusterUv[c].color)[v];
+    }
+    wave_lds_sync();      // (one wave per workgroup: the LDS hand-off must not wait for the arena stores in flight, round 5)
+    for (uint32_t t = lane; t < triCount; t += 64) {
+        const uint8_t* tb = cs.triBase + t * 3u;
+        const uint32_t i0 = tb[0], i1 = tb[1], i2 = tb[2];
+        // CalcFullBary, triangle part
+        const f3 invW{rcpf(cw[i0]), rcpf(cw[i1]), rcpf(cw[i2])};
+        const float n0x = cx[i0] * invW.x, n0y = cy[i0] * invW.x, n1x = cx[i1] * invW.y, n1y = cy[i1] * invW.y, n2x = cx[i2] * invW.z, n2y = cy[i2] * invW.z;
+        const float ax = n2x - n1x, ay = n2y - n1y, bx = n0x - n1x, by = n0y - n1y;
+        const float invDet = rcpf(ax * by - ay * bx);
+        const f3 ddx = f3{n1y - n2y, n2y - n0y, n0y - n1y} * invDet * invW;
+        const f3 ddy = f3{n2x - n1x, n0x - n2x, n1x - n0x} * invDet * invW;
+        ResolveTriangle r;
+        r.n0x = n0x; r.n0y = n0y; r.invW0 = invW.x;
+        r.ddx[0] = ddx.x; r.ddx[1] = ddx.y; r.ddx[2] = ddx.z; r.ddy[0] = ddy.x; r.ddy[1] = ddy.y; r.ddy[2] = ddy.z;
+        r.ddxSum = dot3(ddx, f3{1.0f, 1.0f, 1.0f}); r.ddySum = dot3(ddy, f3{1.0f, 1.0f, 1.0f});
+        r.indices = i0 | (i1 << 8) | (i2 << 16);
+        a.tris[cs.triBase32 + t] = r;
+    }
+    wave_lds_sync();
+}
+// the word that tells the host whether frames like this one should resolve without the tables (its hint for the next frames): cluster triangles against pixels, not tables built
+BRMI_DEV void resolve_setup_feedback(const GBufferArgs& a, uint32_t lane) {
+    if (blockIdx.x == 0u && lane == 0u && a.hostFeedback && a.setupPart != 1u) {
+        const uint64_t tris = (uint64_t)a.counters[CNT_SUM_VERTS_HI];
+        __hip_atomic_store(a.hostFeedback + 1, tris * a.inlineRatio > a.pixelCount ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
 __global__ void __launch_bounds__(64) k_resolve_setup(GBufferArgs a) {
     __shared__ float cx[BRMI_MESHLET_MAX_VERTS], cy[BRMI_MESHLET_MAX_VERTS], cw[BRMI_MESHLET_MAX_VERTS];
     const uint32_t lane = threadIdx.x;
     // part 1 runs while the rasteriser and the phase-2 culling are still at work: it reads the phase-1 count only (final since the compaction)
     const uint32_t firstCluster = a.setupPart == 2u ? min(a.counters[CNT_VISIBLE], a.clusterCapacity) : 0u;
     const uint32_t clusterCount = a.setupPart == 1u ? min(a.counters[CNT_VISIBLE], a.clusterCapacity) : min(a.counters[CNT_VISIBLE] + a.counters[CNT_VISIBLE2], a.clusterCapacity);
-    if (blockIdx.x == 0u && lane == 0u && a.hostFeedback && a.setupPart != 1u) {      // tell the host whether frames like this one should resolve without the tables (its hint for the next frames)
-        const uint64_t tris = (uint64_t)a.counters[CNT_SUM_VERTS_HI];
-        __hip_atomic_store(a.hostFeedback + 1, tris * a.inlineRatio > a.pixelCount ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    for (uint32_t c = firstCluster + blockIdx.x; c < clusterCount; c += gridDim.x) {
-        const ClusterSetup cs = a.setup[c];
-        if (cs.vertBase == BRMI_ARENA_NONE) continue;          // arena full: the pixel pass walks this cluster's data itself
-        const uint32_t vertCount = cs.counts & 0xFFu, triCount = (cs.counts >> 8) & 0xFFu, posFormat = (cs.counts >> 16) & 0xFFu;
-        const m4 objectToClip = load_m4(a.objConst + (size_t)cs.perObjectIndex * OBJ_CONST_FLOATS + 16u);
-        const bool skinned = (cs.counts & BRMI_CS_SKINNED) != 0u;
-        const uint32_t skinSlot = skinned ? a.sc.perMeshInstance[cs.instanceIndex].skinningInstanceSlot : 0xFFFFFFFFu;
-        for (uint32_t v = lane; v < vertCount; v += 64) {
-            f3 p{0.0f, 0.0f, 0.0f};
-            if (posFormat == BRMI_POSITION_FORMAT_FLOAT3) { const float* pp = reinterpret_cast<const float*>(cs.posBase + v * 12u); p = f3{pp[0], pp[1], pp[2]}; }
-            f3 n = oct_decode_normal(*reinterpret_cast<const uint32_t*>(cs.nrmBase + v * 4u));
-            if (skinned) {      // ApplyClodSkinning (clodResolveCommon.hlsli:702-714): once per vertex here, not once per pixel and corner
-                uint32_t joints[8]; float weights[8];
-                load_skin_influences((cs.counts & BRMI_CS_JOINTS) ? cs.nrmBase + cs.jointDelta + v * 32u : nullptr, (cs.counts & BRMI_CS_WEIGHTS) ? cs.nrmBase + cs.weightDelta + v * 32u : nullptr, joints, weights);
-                const m4 skin = build_skin_matrix(a.sc.skinningMatrices, skinSlot, joints, weights);
-                p = xyz(mul_point(p, skin)); n = mul_v3m3(n, skin);
-            }
-            const f4 clip = mul_point(p, objectToClip);
-            cx[v] = clip.x; cy[v] = clip.y; cw[v] = clip.w;
-            a.verts[cs.vertBase + v] = ResolveVertex{p.x, p.y, p.z, n.x, n.y, n.z};
-            if (a.uvs && (cs.counts & BRMI_CS_TEXTURED))
-                for (uint32_t set = 0; set < a.uvSets; set++) { const f2 uv = decode_uv_set(a.clusterUv[c], set, v); a.uvs[(size_t)set * a.vertCapacity + cs.vertBase + v] = make_float2(uv.x, uv.y); }
-            if (a.colors && (cs.counts & BRMI_CS_COLOR)) a.colors[cs.vertBase + v] = reinterpret_cast<const uint32_t*>(a.clusterUv[c].color)[v];
-        }
-        wave_lds_sync();      // (one wave per workgroup: the LDS hand-off must not wait for the arena stores in flight, round 5)
-        for (uint32_t t = lane; t < triCount; t += 64) {
-            const uint8_t* tb = cs.triBase + t * 3u;
-            const uint32_t i0 = tb[0], i1 = tb[1], i2 = tb[2];
-            // CalcFullBary, triangle part
-            const f3 invW{rcpf(cw[i0]), rcpf(cw[i1]), rcpf(cw[i2])};
-            const float n0x = cx[i0] * invW.x, n0y = cy[i0] * invW.x, n1x = cx[i1] * invW.y, n1y = cy[i1] * invW.y, n2x = cx[i2] * invW.z, n2y = cy[i2] * invW.z;
-            const float ax = n2x - n1x, ay = n2y - n1y, bx = n0x - n1x, by = n0y - n1y;
-            const float invDet = rcpf(ax * by - ay * bx);
-            const f3 ddx = f3{n1y - n2y, n2y - n0y, n0y - n1y} * invDet * invW;
-            const f3 ddy = f3{n2x - n1x, n0x - n2x, n1x - n0x} * invDet * invW;
-            ResolveTriangle r;
-            r.n0x = n0x; r.n0y = n0y; r.invW0 = invW.x;
-            r.ddx[0] = ddx.x; r.ddx[1] = ddx.y; r.ddx[2] = ddx.z; r.ddy[0] = ddy.x; r.ddy[1] = ddy.y; r.ddy[2] = ddy.z;
-            r.ddxSum = dot3(ddx, f3{1.0f, 1.0f, 1.0f}); r.ddySum = dot3(ddy, f3{1.0f, 1.0f, 1.0f});
-            r.indices = i0 | (i1 << 8) | (i2 << 16);
-            a.tris[cs.triBase32 + t] = r;
-        }
-        wave_lds_sync();
+    resolve_setup_feedback(a, lane);
+    for (uint32_t c = firstCluster + blockIdx.x; c < clusterCount; c += gridDim.x) resolve_setup_cluster(a, c, lane, cx, cy, cw);
+}
+// The tables follow the draw list (round 6, brmi_raster.hip): on a frame that holds clusters back, a held cluster the re-test never releases is not rasterised, so no key names it and
+// the pixel pass never reads its entries -- they are not made (its place in the arena stays as the compaction reserved it, with whatever it held).  The setup walks the lists
+// k_raster walks, so the two cannot disagree about what is drawn: part 1 the draw list (final since the compaction, like the phase-1 count), part 2 the late list (final since
+// k_retest_held: the launch sits behind the rasteriser stage) and the phase-2 clusters, part 0 all three.  A kernel of its own: frames without a draw list launch k_resolve_setup as it was.
+__global__ void __launch_bounds__(64) k_resolve_setup_listed(GBufferArgs a, const uint32_t* drawList, const uint32_t* lateList) {
+    __shared__ float cx[BRMI_MESHLET_MAX_VERTS], cy[BRMI_MESHLET_MAX_VERTS], cw[BRMI_MESHLET_MAX_VERTS];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t visible1 = min(a.counters[CNT_VISIBLE], a.clusterCapacity);
+    const uint32_t clusterCount = a.setupPart == 1u ? visible1 : min(a.counters[CNT_VISIBLE] + a.counters[CNT_VISIBLE2], a.clusterCapacity);
+    const uint32_t drawCount = a.setupPart != 2u ? min(a.counters[CNT_DRAW1], visible1) : 0u;
+    const uint32_t lateCount = a.setupPart != 1u ? min(a.counters[CNT_LATE1], visible1) : 0u;
+    const uint32_t items = drawCount + lateCount + (clusterCount - visible1);
+    resolve_setup_feedback(a, lane);
+    for (uint32_t item = blockIdx.x; item < items; item += gridDim.x) {      // (wave-uniform: one wave per workgroup)
+        const uint32_t c = item < drawCount ? kconst(drawList)[item] : item < drawCount + lateCount ? kconst(lateList)[item - drawCount] : visible1 + (item - drawCount - lateCount);
+        if (c < clusterCount) resolve_setup_cluster(a, c, lane, cx, cy, cw);
     }
 }
 
@@ -641,12 +665,18 @@ int launch_resolve_setup(brmi_pass* p, hipStream_t s, uint32_t part) {
     GBufferArgs a = gbuffer_args_of(p);
     a.hostFeedback = p->ensureFeedback() ? p->phase2FeedbackDev : nullptr;
     a.setupPart = part;
-    if (part != 0u) {      // (brmi_execute_split: phase-1 clusters beside the rasteriser on the shading stream, phase-2 clusters -- usually a handful -- at the end of the geometry half)
-        hipLaunchKernelGGL(k_resolve_setup, dim3(part == 1u ? 8192 : 512), dim3(64), 0, s, a);
-        BRMI_LAUNCH_CHECK(p, "k_resolve_setup");
+    // (brmi_execute_split: phase-1 clusters beside the rasteriser on the shading stream, phase-2 clusters -- usually a handful -- at the end of the geometry half)
+    const dim3 grid(part == 2u ? 512 : 8192);
+    // a frame whose culling made a draw list (launch_cull; every caller is behind it, parts 0 and 2 behind the rasteriser stage with its re-test too): tables for the
+    // clusters that are drawn -- part 2 takes the late list along with the phase-2 clusters (nothing with a still camera), part 0 finds every list final
+    // (holdThisFrame is written by phase 1 of launch_cull alone and outlives the brmi_execute call: brmi_gbuffer on its own finds the answer of the most recent
+    // phase-1 culling, which is the one whose lists and counters the workspace holds -- a frame's culling clears and refills them before anything here runs)
+    if (p->holdThisFrame) {
+        hipLaunchKernelGGL(k_resolve_setup_listed, grid, dim3(64), 0, s, a, p->wsPtr<uint32_t>(p->ws.drawList), p->wsPtr<uint32_t>(p->ws.lateList));
+        BRMI_LAUNCH_CHECK(p, "k_resolve_setup_listed");
         return BRMI_OK;
     }
-    hipLaunchKernelGGL(k_resolve_setup, dim3(8192), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(k_resolve_setup, grid, dim3(64), 0, s, a);
     BRMI_LAUNCH_CHECK(p, "k_resolve_setup");
     return BRMI_OK;
 }
