@@ -126,6 +126,17 @@ class StreamingBuffers(C.Structure):
                 ("touchedGroups", vp), ("touchedCapacity", u32), ("counts", vp), ("scratch", vp), ("scratchBytes", u64)]
 
 
+class DebugViewBuffers(C.Structure):
+    """brmi_debug_view_buffers (include/brmi.h): caller-owned targets of the debug view."""
+    _fields_ = [("structSize", u32), ("reserved", u32), ("payload", vp), ("payloadBytes", u64), ("image", vp), ("imageBytes", u64)]
+
+
+# perFrame.outputType values with a payload kernel (brmi_output_type; the reference's OUTPUT_* names without the prefix)
+OUTPUT_TYPES = {"COLOR": 0, "NORMAL": 1, "ALBEDO": 2, "METALLIC": 3, "ROUGHNESS": 4, "EMISSIVE": 5, "AO": 6, "DEPTH": 7, "MESHLETS": 10,
+                "LIGHT_CLUSTER_ID": 12, "LIGHT_CLUSTER_LIGHT_COUNT": 13, "MOTION_VECTORS": 14, "GEOMETRY_GROUP": 35}
+PER_FRAME_OUTPUT_TYPE_WORD = 12      # brmi_per_frame::outputType as a u32 index
+
+
 class Counters(C.Structure):
     _fields_ = [(n, u32) for n in ("instancesTested instancesVisible nodesVisited bucketRecords meshletsTested "
                                    "visibleClusters visibleClustersPhase2 droppedRecords droppedClusters "
@@ -229,7 +240,8 @@ BRMI_EXPORTS = ["brmi_abi_version", "brmi_default_config", "brmi_create", "brmi_
                 "brmi_update", "brmi_execute", "brmi_execute_split", "brmi_destroy", "brmi_last_error", "brmi_clear_visibility", "brmi_cull",
                 "brmi_raster", "brmi_depth_copy", "brmi_build_hzb", "brmi_invalidate_hzb", "brmi_set_history_source", "brmi_gbuffer", "brmi_light_clustering",
                 "brmi_shade", "brmi_set_shade_slabs", "brmi_read_counters", "brmi_stage_times", "brmi_set_timed_stages", "brmi_algorithmic_bytes", "brmi_algorithmic_bytes_launched", "brmi_debug_arith", "brmi_debug_arith_in_range", "brmi_debug_read_bin_records", "brmi_debug_wide_triangles", "brmi_debug_lean_clusters", "brmi_debug_read_lean_queue", "brmi_debug_read_held",
-                "brmi_streaming_scratch_bytes", "brmi_set_streaming", "brmi_streaming_feedback", "brmi_set_sampler_anisotropy", "brmi_debug_sample_grad"]
+                "brmi_streaming_scratch_bytes", "brmi_set_streaming", "brmi_streaming_feedback", "brmi_set_sampler_anisotropy", "brmi_debug_sample_grad",
+                "brmi_abi_minor", "brmi_debug_view_bytes", "brmi_set_debug_view", "brmi_debug_view"]
 
 
 def brmi_lib():
@@ -279,5 +291,11 @@ def brmi_lib():
         if hasattr(lib, "brmi_set_sampler_anisotropy"):      # (absent from an older build of the same ABI loaded through BRMI_LIB_PATH for an A/B run)
             lib.brmi_set_sampler_anisotropy.argtypes = [vp, vp, u32]
             lib.brmi_debug_sample_grad.argtypes = [C.POINTER(SceneBuffers), vp, u32, u32, u32, vp, vp, vp, vp, u32, vp]
+        if hasattr(lib, "brmi_set_debug_view"):
+            lib.brmi_abi_minor.restype = u32
+            lib.brmi_debug_view_bytes.argtypes = [u32, u32]
+            lib.brmi_debug_view_bytes.restype = u64
+            lib.brmi_set_debug_view.argtypes = [vp, C.POINTER(DebugViewBuffers)]
+            lib.brmi_debug_view.argtypes = [vp, vp]
         _brmi_lib = lib
     return _brmi_lib

@@ -207,6 +207,7 @@ using namespace brmi;
 extern "C" {
 
 uint32_t brmi_abi_version(void) { return BRMI_ABI_VERSION; }
+uint32_t brmi_abi_minor(void) { return BRMI_ABI_MINOR; }
 
 void brmi_default_config(brmi_config* cfg, uint32_t width, uint32_t height) {
     if (!cfg) return;
@@ -771,6 +772,40 @@ int brmi_streaming_feedback(brmi_pass* p, brmi_stream stream) {
     if (!p->streaming.on) return brmi::fail(p, BRMI_ERR_STATE, "brmi_streaming_feedback: no streaming buffers bound (brmi_set_streaming)");
     return brmi::launch_streaming_feedback(p, static_cast<hipStream_t>(stream));
 }
+uint64_t brmi_debug_view_bytes(uint32_t width, uint32_t height) { return (uint64_t)((width + 7u) / 8u) * ((height + 7u) / 8u) * 64u * 8u; }
+int brmi_set_debug_view(brmi_pass* p, const brmi_debug_view_buffers* b) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (!b) { p->debugView.on = false; return BRMI_OK; }
+    if (b->structSize != sizeof(brmi_debug_view_buffers)) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_debug_view: structSize %u, expected %zu", b->structSize, sizeof(brmi_debug_view_buffers));
+    if (p->stripes.count > 1u) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_debug_view: not with the interleaved partition (stripeCount %u): the compact surfaces' pixel rows are not the frame's", p->stripes.count);
+    if (!b->payload) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_debug_view: the payload pointer is null");
+    if (reinterpret_cast<uintptr_t>(b->payload) & 15u) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_debug_view: the payload must be 16 B aligned");
+    const uint64_t need = brmi_debug_view_bytes(p->cfg.width, p->cfg.height), needImage = (uint64_t)p->cfg.width * p->cfg.height * 4u;
+    if (b->payloadBytes < need) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_debug_view: the payload holds %llu bytes, %u x %u pixels need %llu", (unsigned long long)b->payloadBytes, p->cfg.width, p->cfg.height, (unsigned long long)need);
+    if (b->image && ((reinterpret_cast<uintptr_t>(b->image) & 3u) || b->imageBytes < needImage))
+        return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_debug_view: the image holds %llu bytes (4 B aligned), %u x %u pixels need %llu", (unsigned long long)b->imageBytes, p->cfg.width, p->cfg.height, (unsigned long long)needImage);
+    p->debugView.b = *b; p->debugView.on = true;
+    return BRMI_OK;
+}
+// Why the pass cannot write the view perFrame.outputType asks for (0: it can).  Host state only: brmi_execute_split asks BEFORE it launches anything, so a
+// refused mode leaves no half-issued frame behind.
+static int debug_view_refusal(brmi_pass* p) {
+    const uint32_t mode = p->pfHost.outputType;
+    if (!brmi::debug_view_mode_built(mode)) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_debug_view: outputType %u is not a debug view of this path (brmi_output_type lists the ones it builds)", mode);
+    if ((mode == BRMI_OUTPUT_LIGHT_CLUSTER_ID || mode == BRMI_OUTPUT_LIGHT_CLUSTER_LIGHT_COUNT) && !p->cfg.enableClusteredLighting)
+        return brmi::fail(p, BRMI_ERR_INVALID, "brmi_debug_view: outputType %u needs enableClusteredLighting", mode);
+    if (!p->debugView.on) return brmi::fail(p, BRMI_ERR_STATE, "brmi_debug_view: no debug target bound (brmi_set_debug_view)");
+    if (p->stripes.count > 1u) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_debug_view: not with the interleaved partition");
+    return BRMI_OK;
+}
+int brmi_debug_view(brmi_pass* p, brmi_stream stream) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (!p->setupDone) return brmi::fail(p, BRMI_ERR_STATE, "brmi_debug_view: call brmi_setup first");
+    if (!p->updated) return brmi::fail(p, BRMI_ERR_STATE, "brmi_debug_view: call brmi_update first (the view is perFrame.outputType of the last update)");
+    if (p->pfHost.outputType == BRMI_OUTPUT_COLOR) return BRMI_OK;
+    if (int rc = debug_view_refusal(p)) return rc;
+    return brmi::launch_debug_view(p, static_cast<hipStream_t>(stream));
+}
 int brmi_build_hzb(brmi_pass* p, brmi_stream stream) {
     CHECK_READY(p); hipStream_t s = static_cast<hipStream_t>(stream);
     if (!p->cfg.enableOcclusionCulling) return brmi::fail(p, BRMI_ERR_STATE, "brmi_build_hzb: the pass was created without enableOcclusionCulling");
@@ -834,6 +869,9 @@ int brmi_execute(brmi_pass* p, brmi_stream stream) { return brmi_execute_split(p
 int brmi_execute_split(brmi_pass* p, brmi_stream stream, brmi_stream shadeStream) {
     CHECK_READY(p);
     int rc;
+    // a debug view the pass cannot write is refused here, before the frame's first launch and before any of its bookkeeping
+    const bool debugView = p->debugView.on && p->pfHost.outputType != BRMI_OUTPUT_COLOR;
+    if (debugView && (rc = debug_view_refusal(p))) return rc;
     p->executesSinceTimes++;
     const bool split = shadeStream != stream;
     p->splitFrame = split;
@@ -923,6 +961,8 @@ int brmi_execute_split(brmi_pass* p, brmi_stream stream, brmi_stream shadeStream
     rc = brmi_shade(p, stream);
     p->shadeSharesChip = false;
     if (rc) return rc;
+    // the debug payload of perFrame.outputType, from the surfaces the frame has just made (behind the shading stage, on its stream, in front of the frame's end)
+    if (debugView && (rc = brmi_debug_view(p, stream))) return rc;
     if (split) { BRMI_HIP(p, hipEventRecord(p->frameDone, static_cast<hipStream_t>(stream))); p->frameDoneRecorded = true; }
     p->splitFrame = false;          // (the stage entry points, called on their own, are not part of a split frame)
     return BRMI_OK;

@@ -408,6 +408,7 @@ struct brmi_pass {
     std::vector<brmi::FlatNode> hostFlatNodes; std::vector<brmi::FlatLeaf> hostFlatLeaves; std::vector<brmi::InstanceWalk> hostInstanceWalk;   // flat traversal tables (brmi_set_scene)
     brmi::Workspace ws{};
     struct { bool on = false; brmi_streaming_buffers b{}; uint32_t groupCount = 0, activeGroupScanCount = 0; } streaming;      // brmi_set_streaming (cleared by brmi_set_scene)
+    struct { bool on = false; brmi_debug_view_buffers b{}; } debugView;      // brmi_set_debug_view
     const uint32_t* samplerAniso = nullptr;      // brmi_set_sampler_anisotropy: device words, one per sampler of the scene (cleared by brmi_set_scene)
     brmi_camera camHost{};
     brmi_per_frame pfHost{};
@@ -452,6 +453,8 @@ int launch_expand_luts(brmi_pass* p, hipStream_t s);
 int launch_meshlet_boxes(brmi_pass* p, hipStream_t s);      // brmi_setup: the per-meshlet boxes of the draw list's tests, from the page contents
 int launch_shade(brmi_pass* p, hipStream_t s);
 int launch_streaming_feedback(brmi_pass* p, hipStream_t s);
+bool debug_view_mode_built(uint32_t mode);                  // brmi_debugview.hip: the outputTypes with a payload kernel
+int launch_debug_view(brmi_pass* p, hipStream_t s);
 int launch_debug_sample_grad(const brmi_scene_buffers& sc, const uint32_t* maxAnisotropy, uint32_t textureIndex, uint32_t samplerIndex, bool uniformBinding, const float* uv, const float* ddx, const float* ddy,
                              float* outRGBA, uint32_t n, hipStream_t s);
 inline StreamArgs stream_args_of(const brmi_pass* p) {

@@ -76,6 +76,8 @@ class VisibilityRenderer:
         self.device_arrays = dict(scene.device_arrays)      # this pass's own copies (two passes in flight each have their camera buffers)
         self._check(self.lib.brmi_set_scene(self._h, C.byref(self.sb)), "brmi_set_scene")
         self._anisotropy = None      # set_anisotropy's table
+        self._debug_mode, self._debug_view, self._pf_own = 0, None, None      # set_debug_view: outputType, the targets, this pass's per-frame record
+        self._frame_index = 0        # of the last brmi_update
         self.descs = {}
 
         def cb(_user, d):
@@ -125,8 +127,9 @@ class VisibilityRenderer:
         current stream into this pass's camera buffers, then brmi_update with the host copy of the same camera."""
         self.device_arrays["cameras"].copy_(cameras_dev, non_blocking=True)
         self.device_arrays["cullingCameras"].copy_(culling_cameras_dev, non_blocking=True)
-        upd = capi.FrameUpdate(cameras_host.ctypes.data, self.scene.per_frame_host().ctypes.data, frame_index)
+        upd = capi.FrameUpdate(cameras_host.ctypes.data, self._per_frame_host(self.scene).ctypes.data, frame_index)
         self._check(self.lib.brmi_update(self._h, C.byref(upd), self._s()), "brmi_update")
+        self._frame_index = frame_index
         self._cam_bytes = cameras_host      # update() of a later frame repeats this camera
 
     def set_band(self, y0, y1):
@@ -134,13 +137,24 @@ class VisibilityRenderer:
         self._check(self.lib.brmi_set_band(self._h, capi.u32(int(y0)), capi.u32(int(y1))), "brmi_set_band")
         self.band = (int(y0), int(y1))
 
+    def _per_frame_host(self, src):
+        """The scene's per-frame record; with a debug view set, this pass's own copy of it with perFrame.outputType filled in (scenes are shared)."""
+        pf = src.per_frame_host()
+        mode = self._debug_mode
+        if not mode:
+            return pf
+        self._pf_own = np.array(pf, copy=True)
+        self._pf_own.view(np.uint32)[capi.PER_FRAME_OUTPUT_TYPE_WORD] = mode
+        return self._pf_own
+
     def update(self, frame_index=0):
+        self._frame_index = frame_index
         if getattr(self, "_cam_bytes", None) is not None:
-            upd = capi.FrameUpdate(self._cam_bytes.ctypes.data, self.scene.per_frame_host().ctypes.data, frame_index)
+            upd = capi.FrameUpdate(self._cam_bytes.ctypes.data, self._per_frame_host(self.scene).ctypes.data, frame_index)
             self._check(self.lib.brmi_update(self._h, C.byref(upd), self._s()), "brmi_update")
             return
         src = getattr(self, "_cam_scene", self.scene)
-        cam, pf = src.camera_host(), src.per_frame_host()
+        cam, pf = src.camera_host(), self._per_frame_host(src)
         upd = capi.FrameUpdate(cam.ctypes.data, pf.ctypes.data, frame_index)
         self._check(self.lib.brmi_update(self._h, C.byref(upd), self._s()), "brmi_update")
 
@@ -352,6 +366,59 @@ class VisibilityRenderer:
         self._check(self.lib.brmi_set_sampler_anisotropy(self._h, table.data_ptr(), capi.u32(count)), "brmi_set_sampler_anisotropy")
         self._anisotropy = table
 
+    # -- debug views (brmi_set_debug_view, perFrame.outputType) ------------------------------------
+    def set_debug_view(self, mode, fill=0, check=True):
+        """The debug view of the frames from the next update() on: a perFrame.outputType number or the reference's name without the OUTPUT_ prefix
+        ("meshlets", "LIGHT_CLUSTER_LIGHT_COUNT", ...); None, 0 or "color" unbinds and gives the ordinary frames again.  Allocates the payload and the
+        image target (this pass's own tensors), fills the payload with the sentinel and every byte of the image with `fill` (pixels without geometry
+        keep it), and repeats the last update() -- same camera, same frame index -- with outputType in this pass's per-frame record.  A number the library
+        has no view for is refused here; check=False lets it through to the library, whose next execute() refuses it before it launches anything."""
+        torch = self.torch
+        if isinstance(mode, str):
+            key = mode.upper()
+            key = key[len("OUTPUT_"):] if key.startswith("OUTPUT_") else key
+            if key not in capi.OUTPUT_TYPES:
+                raise BrmiError(f"set_debug_view: no debug view named {mode!r} (known: {', '.join(sorted(capi.OUTPUT_TYPES))})")
+            mode = capi.OUTPUT_TYPES[key]
+        mode = int(mode or 0)
+        if check and mode not in capi.OUTPUT_TYPES.values():
+            raise BrmiError(f"set_debug_view: outputType {mode} is not a debug view of this path (known: {', '.join(sorted(capi.OUTPUT_TYPES))})")
+        if self._debug_view is not None:
+            torch.cuda.synchronize(self.device)      # a frame in flight may still be writing the targets that are about to be dropped
+        if mode == 0:
+            self._check(self.lib.brmi_set_debug_view(self._h, None), "brmi_set_debug_view")
+            self._debug_view = None
+        else:
+            payload = torch.full((int(self.lib.brmi_debug_view_bytes(self.W, self.H)) // 4,), -1, dtype=torch.int32, device=self.device)
+            image = torch.full((self.H, self.W, 4), int(fill), dtype=torch.uint8, device=self.device)
+            b = capi.DebugViewBuffers()
+            b.structSize = C.sizeof(capi.DebugViewBuffers)
+            b.payload, b.payloadBytes = payload.data_ptr(), payload.numel() * 4
+            b.image, b.imageBytes = image.data_ptr(), image.numel()
+            self._check(self.lib.brmi_set_debug_view(self._h, C.byref(b)), "brmi_set_debug_view")
+            self._debug_view = dict(payload=payload, image=image)
+        self._debug_mode = mode
+        # the device record too: brmi_frame_update::perFrameHost is by contract the host copy of that buffer (the library picks the kernel from the host
+        # copy, and its frame snapshot carries the device one along; no kernel reads the field today)
+        pf = self.device_arrays["perFrame"]
+        words = torch.from_numpy(np.array([mode], dtype=np.int32)).to(self.device)
+        pf.view(torch.int32)[capi.PER_FRAME_OUTPUT_TYPE_WORD: capi.PER_FRAME_OUTPUT_TYPE_WORD + 1].copy_(words)
+        self.update(self._frame_index)
+
+    def debug_payload(self):
+        """(H, W, 2) uint32: the last frame's debug payload, untiled; (0xFFFFFFFF, 0xFFFFFFFF) where there is no geometry."""
+        if self._debug_view is None:
+            raise BrmiError("debug_payload: set_debug_view first")
+        self.torch.cuda.synchronize(self.device)
+        return detile(self._debug_view["payload"].cpu().numpy().view(np.uint32).reshape(-1, 2), self.W, self.H)
+
+    def debug_image(self):
+        """(H, W, 4) uint8: the last frame's debug view as sRGB colour; pixels without geometry keep set_debug_view's fill."""
+        if self._debug_view is None:
+            raise BrmiError("debug_image: set_debug_view first")
+        self.torch.cuda.synchronize(self.device)
+        return self._debug_view["image"].cpu().numpy()
+
     def set_history_source(self, other):
         """Frames in flight: phase 1 tests against the depth chain `other` built for the frame before (None unlinks)."""
         self._check(self.lib.brmi_set_history_source(self._h, other._h if other is not None else None), "brmi_set_history_source")
@@ -386,6 +453,7 @@ class VisibilityRenderer:
             self._h = None
             # every byte the pass used is caller-owned: drop the resource tensors and the uploaded scene with the pass
             self.res = {}
+            self._debug_view = None
             self._scene_keep = []
             self.device_arrays = {}
             if hasattr(self.scene, "device_arrays"):

@@ -2,7 +2,10 @@
 """Render a Wavefront OBJ or a glTF 2.0 file (.gltf / .glb) through the whole path on an MI355X and write the lit frame as a PNG
 (Reinhard + sRGB).
 
-    python examples/render_obj.py model.obj|scene.glb out.png [--size 1920x1080] [--lights 32] [--features 0]
+    python examples/render_obj.py model.obj|scene.glb out.png [--size 1920x1080] [--lights 32] [--features 0] [--view NAME]
+
+--view NAME writes a debug view of the frame instead (perFrame.outputType: normal, albedo, metallic, roughness, emissive, ao, depth, meshlets,
+geometry_group, light_cluster_id, light_cluster_light_count, motion_vectors); pixels without geometry are black.
 """
 import argparse
 import os
@@ -31,6 +34,7 @@ def main():
     ap.add_argument("obj"); ap.add_argument("png")
     ap.add_argument("--size", default="1920x1080"); ap.add_argument("--lights", type=int, default=32); ap.add_argument("--features", type=int, default=0)
     ap.add_argument("--anisotropy", type=int, default=0, metavar="N", help="maxAnisotropy of every sampler, 1..16 (default: off, the isotropic sampler)")
+    ap.add_argument("--view", default=None, metavar="NAME", help="write this debug view (e.g. meshlets) instead of the tone-mapped frame")
     a = ap.parse_args()
     from basicrenderer_amd import Scene
     from basicrenderer_amd.obj import frame_view, load_obj
@@ -47,7 +51,13 @@ def main():
     r = VisibilityRenderer(sc, occlusion=True)
     if a.anisotropy > 0:
         r.set_anisotropy(a.anisotropy)
+    if a.view:
+        r.set_debug_view(a.view)
     r.execute(); r.execute()
+    if a.view:
+        write_png(a.png, np.ascontiguousarray(r.debug_image()[..., :3]))
+        print(f"{a.obj}: debug view {a.view} -> {a.png}")
+        return
     hdr = r.hdr().view(np.float16).reshape(h, w, 4)[..., :3].astype(np.float32)
     ldr = hdr / (1.0 + hdr)
     srgb = np.where(ldr <= 0.0031308, 12.92 * ldr, 1.055 * np.power(np.maximum(ldr, 1e-8), 1 / 2.4) - 0.055)

@@ -26,6 +26,9 @@ extern "C" {
 #endif
 
 #define BRMI_ABI_VERSION 1u
+/* Additions that leave every ABI-1 host binary compatible (new entry points, no changed layout) raise the minor number.  1: brmi_set_debug_view,
+ * brmi_debug_view, brmi_debug_view_bytes. */
+#define BRMI_ABI_MINOR 1u
 
 typedef enum brmi_status {
     BRMI_OK            = 0,
@@ -134,6 +137,39 @@ typedef struct brmi_streaming_buffers {
     void* scratch;                           uint64_t scratchBytes;      /* >= brmi_streaming_scratch_bytes(lodGroupCount), 16 B aligned; the library's between the frame's first culling launch and brmi_streaming_feedback */
 } brmi_streaming_buffers;
 
+/* ---- debug views: perFrame.outputType (BR/shaders/Include/outputTypes.hlsli) ------------------
+ * The modes this path builds.  The payload is the reference's (Include/debugPayload.hlsli): one uint2 per pixel, (0xFFFFFFFF, 0xFFFFFFFF) where the
+ * pixel has no geometry; float3 modes hold three RNE halves in x low, x high, y low, integer modes hold (v, 0).  The material modes (ALBEDO, METALLIC,
+ * ROUGHNESS, AO, MOTION_VECTORS) pack what the G-buffer planes HOLD, i.e. the value after the plane's format quantised it; the reference packs the
+ * material inputs before that.  Every other outputType (MODEL_NORMALS, SW_RASTER, MATERIAL_SELECTED_MIP, the IBL / VSM / Reyes /
+ * voxel / transparency modes) is refused by brmi_debug_view. */
+typedef enum brmi_output_type {
+    BRMI_OUTPUT_COLOR = 0,                        /* the lit frame: no debug payload */
+    BRMI_OUTPUT_NORMAL = 1,                       /* normals.xyz * 0.5 + 0.5 */
+    BRMI_OUTPUT_ALBEDO = 2,
+    BRMI_OUTPUT_METALLIC = 3,
+    BRMI_OUTPUT_ROUGHNESS = 4,
+    BRMI_OUTPUT_EMISSIVE = 5,
+    BRMI_OUTPUT_AO = 6,                           /* albedo.a */
+    BRMI_OUTPUT_DEPTH = 7,                        /* |linear depth| * 0.1 */
+    BRMI_OUTPUT_MESHLETS = 10,                    /* page-local meshlet index of the pixel's visible cluster */
+    BRMI_OUTPUT_LIGHT_CLUSTER_ID = 12,            /* the light cluster's depth slice (lighting.hlsli:509), at most lightClusterSize[2] */
+    BRMI_OUTPUT_LIGHT_CLUSTER_LIGHT_COUNT = 13,   /* numLights of the pixel's light cluster; needs enableClusteredLighting */
+    BRMI_OUTPUT_MOTION_VECTORS = 14,              /* (mv * 0.5 + 0.5, 0.5) */
+    BRMI_OUTPUT_GEOMETRY_GROUP = 35               /* LOD group id of the pixel's visible cluster */
+} brmi_output_type;
+
+/* Caller-owned device memory of the debug view (never part of brmi_declare's list).  payload: one uint2 per pixel in the surfaces' tiled 8x8 layout,
+ * brmi_debug_view_bytes(width, height) bytes (whole tiles), 16 B aligned; the library writes every pixel of the band, the sentinel included.  image:
+ * optional (NULL = payload only) rgba8, ROW-MAJOR width x height x 4 bytes -- the one surface meant to be looked at; pixels whose payload is the sentinel
+ * are NOT written (the reference's resolve discards them), so what the caller put there shows through. */
+typedef struct brmi_debug_view_buffers {
+    uint32_t structSize;              /* sizeof(brmi_debug_view_buffers) */
+    uint32_t reserved;
+    void*    payload;  uint64_t payloadBytes;
+    void*    image;    uint64_t imageBytes;      /* >= width * height * 4 when image is bound */
+} brmi_debug_view_buffers;
+
 /* ---- graph resources the pass declares (DeclareResourceUsages) ---------------------------- */
 typedef enum brmi_resource_id {
     BRMI_RES_VISIBILITY = 0,          /* Builtin::PrimaryCamera::VisibilityTexture  u64/px, tiled 8x8 */
@@ -207,6 +243,7 @@ enum brmi_stage {
 
 /* ---- lifecycle (ComputePass phases) -------------------------------------------------------- */
 uint32_t    brmi_abi_version(void);
+uint32_t    brmi_abi_minor(void);
 int         brmi_create(const brmi_config* cfg, brmi_pass** out);
 int         brmi_declare(brmi_pass* pass, brmi_declare_cb cb, void* user);            /* DeclareResourceUsages */
 int         brmi_set_scene(brmi_pass* pass, const brmi_scene_buffers* scene);          /* provider resolution   */
@@ -245,6 +282,20 @@ int brmi_set_streaming(brmi_pass* pass, const brmi_streaming_buffers* streaming)
  * samplerCount words, caller-owned, read by the frame's G-buffer launch.  NULL switches it off and gives exactly the frames of a pass that never called it.
  * Call after brmi_set_scene (which forgets the binding).  BRMI_ERR_INVALID: count != the scene's samplerCount. */
 int brmi_set_sampler_anisotropy(brmi_pass* pass, const uint32_t* maxAnisotropy, uint32_t count);
+
+/* Debug views.  brmi_set_debug_view binds the targets (NULL unbinds and gives exactly the frames of a pass that never called it); with a target bound and
+ * perFrame.outputType != 0, brmi_execute / brmi_execute_split run brmi_debug_view behind the shading stage (on the shading stream); an outputType the stage
+ * would refuse makes them fail BEFORE anything is launched.  The lit HDR frame and
+ * every plane are written as always (deferred.hlsl:62-63 does the same): nothing of the frame depends on the mode.  Row bands are supported (only the band's
+ * rows are written); the INTERLEAVED partition (brmi_config::stripeCount > 1) is refused, because the pixel rows of its compact surfaces are not the
+ * frame's rows and a debug image of them would not be the picture.  Refusals: BRMI_ERR_INVALID for a wrong structSize, a null / misaligned / short
+ * payload, a short image, stripes. */
+uint64_t brmi_debug_view_bytes(uint32_t width, uint32_t height);
+int brmi_set_debug_view(brmi_pass* pass, const brmi_debug_view_buffers* view);
+/* The stage: the payload kernel for the outputType of the last brmi_update, then the resolve where an image is bound.  Reads the surfaces of the frame
+ * the pass last rendered; returns without a launch for outputType == 0.  BRMI_ERR_STATE before brmi_setup / brmi_update or without a bound target,
+ * BRMI_ERR_INVALID for an outputType outside brmi_output_type (or a light-cluster mode without enableClusteredLighting). */
+int brmi_debug_view(brmi_pass* pass, brmi_stream stream);
 
 /* Rows [bandY0, bandY1) of the frame this GPU renders FROM THE NEXT FRAME ON (multiples of 8; passes created with brmi_config::dynamicBand): call it between frames,
  * before the frame's brmi_update.  The screen-tile split of SURVEY.md 8(e) with regions whose boundaries follow the cost of the frames before, so that every GPU takes
