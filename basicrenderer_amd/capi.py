@@ -131,6 +131,20 @@ class DebugViewBuffers(C.Structure):
     _fields_ = [("structSize", u32), ("reserved", u32), ("payload", vp), ("payloadBytes", u64), ("image", vp), ("imageBytes", u64)]
 
 
+class EnvironmentInfo(C.Structure):
+    """brmi_environment_info (include/brmi_types.h): the reference's EnvironmentInfo, 128 B."""
+    _fields_ = [("cubeMapDescriptorIndex", u32), ("prefilteredCubemapDescriptorIndex", u32), ("sphericalHarmonicsScale", f32),
+                ("sphericalHarmonics", C.c_int32 * 27), ("pad", u32 * 2)]
+
+
+class EnvironmentBuffers(C.Structure):
+    """brmi_environment_buffers (include/brmi.h): caller-owned device tables of the image-based lighting."""
+    _fields_ = [("structSize", u32), ("specularIBL", u32), ("environments", vp), ("environmentCount", u32), ("cubemaps", vp), ("cubemapCount", u32)]
+
+
+SH_FLOAT_SCALE = 100                      # BRMI_SH_FLOAT_SCALE
+PER_FRAME_ACTIVE_ENVIRONMENT_WORD = 11    # brmi_per_frame::activeEnvironmentIndex as a u32 index
+
 # perFrame.outputType values with a payload kernel (brmi_output_type; the reference's OUTPUT_* names without the prefix)
 OUTPUT_TYPES = {"COLOR": 0, "NORMAL": 1, "ALBEDO": 2, "METALLIC": 3, "ROUGHNESS": 4, "EMISSIVE": 5, "AO": 6, "DEPTH": 7, "MESHLETS": 10,
                 "LIGHT_CLUSTER_ID": 12, "LIGHT_CLUSTER_LIGHT_COUNT": 13, "MOTION_VECTORS": 14, "GEOMETRY_GROUP": 35}
@@ -241,7 +255,8 @@ BRMI_EXPORTS = ["brmi_abi_version", "brmi_default_config", "brmi_create", "brmi_
                 "brmi_raster", "brmi_depth_copy", "brmi_build_hzb", "brmi_invalidate_hzb", "brmi_set_history_source", "brmi_gbuffer", "brmi_light_clustering",
                 "brmi_shade", "brmi_set_shade_slabs", "brmi_read_counters", "brmi_stage_times", "brmi_set_timed_stages", "brmi_algorithmic_bytes", "brmi_algorithmic_bytes_launched", "brmi_debug_arith", "brmi_debug_arith_in_range", "brmi_debug_read_bin_records", "brmi_debug_wide_triangles", "brmi_debug_lean_clusters", "brmi_debug_read_lean_queue", "brmi_debug_read_held",
                 "brmi_streaming_scratch_bytes", "brmi_set_streaming", "brmi_streaming_feedback", "brmi_set_sampler_anisotropy", "brmi_debug_sample_grad",
-                "brmi_abi_minor", "brmi_debug_view_bytes", "brmi_set_debug_view", "brmi_debug_view"]
+                "brmi_abi_minor", "brmi_debug_view_bytes", "brmi_set_debug_view", "brmi_debug_view",
+                "brmi_set_environment", "brmi_debug_ibl_lookup", "brmi_debug_ibl"]
 
 
 def brmi_lib():
@@ -297,5 +312,9 @@ def brmi_lib():
             lib.brmi_debug_view_bytes.restype = u64
             lib.brmi_set_debug_view.argtypes = [vp, C.POINTER(DebugViewBuffers)]
             lib.brmi_debug_view.argtypes = [vp, vp]
+        if hasattr(lib, "brmi_set_environment"):
+            lib.brmi_set_environment.argtypes = [vp, C.POINTER(EnvironmentBuffers)]
+            lib.brmi_debug_ibl_lookup.argtypes = [C.POINTER(EnvironmentBuffers), u32, vp, vp, vp, u32, vp]
+            lib.brmi_debug_ibl.argtypes = [vp, C.POINTER(EnvironmentBuffers), u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]
         _brmi_lib = lib
     return _brmi_lib

@@ -639,6 +639,8 @@ int brmi_setup(brmi_pass* p, const brmi_resource_binding* b, uint32_t n, brmi_st
 int brmi_update(brmi_pass* p, const brmi_frame_update* u, brmi_stream stream) {
     if (!p || !u || !u->mainCameraHost || !u->perFrameHost) return BRMI_ERR_INVALID;
     if (!p->setupDone) return fail(p, BRMI_ERR_STATE, "brmi_update: call brmi_setup first");
+    if (p->env.on && u->perFrameHost->activeEnvironmentIndex >= p->env.b.environmentCount)      // (before anything of the pass changes: the frame before stays the last one)
+        return fail(p, BRMI_ERR_INVALID, "brmi_update: perFrame.activeEnvironmentIndex %u, the bound environment table has %u entries", u->perFrameHost->activeEnvironmentIndex, p->env.b.environmentCount);
     p->camHost = *u->mainCameraHost; p->pfHost = *u->perFrameHost;
     const brmi_per_frame& pf = p->pfHost;
     if (pf.lightClusterGridSizeX != p->cfg.lightClusterSize[0] || pf.lightClusterGridSizeY != p->cfg.lightClusterSize[1] || pf.lightClusterGridSizeZ != p->cfg.lightClusterSize[2])
@@ -765,6 +767,18 @@ int brmi_set_sampler_anisotropy(brmi_pass* p, const uint32_t* maxAnisotropy, uin
     if (!p->haveScene) return brmi::fail(p, BRMI_ERR_STATE, "brmi_set_sampler_anisotropy: brmi_set_scene first (the table has one word per sampler of the scene)");
     if (count != p->scene.samplerCount) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_sampler_anisotropy: count %u, the scene has %u samplers", count, p->scene.samplerCount);
     p->samplerAniso = maxAnisotropy;
+    return BRMI_OK;
+}
+int brmi_set_environment(brmi_pass* p, const brmi_environment_buffers* e) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (!e) { if (p->env.on) p->updateSerial++; p->env.on = false; p->env.b = brmi_environment_buffers{}; return BRMI_OK; }
+    if (e->structSize != sizeof(brmi_environment_buffers)) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_environment: structSize %u, expected %zu", e->structSize, sizeof(brmi_environment_buffers));
+    if ((!e->environments && e->environmentCount) || (!e->cubemaps && e->cubemapCount)) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_environment: a null table with a non-zero count");
+    if (e->environmentCount == 0u || !e->environments) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_environment: environmentCount is 0 (NULL unbinds)");
+    if (p->updated && p->pfHost.activeEnvironmentIndex >= e->environmentCount)
+        return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_environment: the last brmi_update's activeEnvironmentIndex is %u, the table has %u entries", p->pfHost.activeEnvironmentIndex, e->environmentCount);
+    p->env.b = *e; p->env.on = true;
+    p->updateSerial++;       // the frame constants fold the environment's coefficients: re-evaluated by the next stage call
     return BRMI_OK;
 }
 int brmi_streaming_feedback(brmi_pass* p, brmi_stream stream) {
@@ -1138,6 +1152,20 @@ int brmi_debug_arith_in_range(const float* a, float* outRcp, float* outSqrt, flo
     return hipGetLastError() == hipSuccess ? BRMI_OK : BRMI_ERR_HIP;
 }
 
+int brmi_debug_ibl_lookup(const brmi_environment_buffers* env, uint32_t cubemapIndex, const float* directions, const float* lods, float* outRGBA, uint32_t n, brmi_stream stream) {
+    if (!env || env->structSize != sizeof(brmi_environment_buffers) || !directions || !lods || !outRGBA) return BRMI_ERR_INVALID;
+    if (n == 0u) return BRMI_OK;
+    return brmi::launch_debug_ibl_lookup(*env, cubemapIndex, directions, lods, outRGBA, n, static_cast<hipStream_t>(stream));
+}
+int brmi_debug_ibl(brmi_pass* p, const brmi_environment_buffers* env, uint32_t environmentIndex, const float* normals, const uint32_t* albedo, const uint32_t* metallicRoughness, const uint64_t* coat,
+                   const uint64_t* emissive, const uint64_t* fuzz, const float* viewWS, float* outDiffuse, float* outSpecular, uint32_t n, brmi_stream stream) {
+    CHECK_READY(p);
+    if (!env || env->structSize != sizeof(brmi_environment_buffers) || !env->environments || environmentIndex >= env->environmentCount)
+        return brmi::fail(p, BRMI_ERR_INVALID, "brmi_debug_ibl: no such environment (structSize, table or index)");
+    if (!normals || !albedo || !metallicRoughness || !coat || !emissive || !fuzz || !viewWS || !outDiffuse || !outSpecular) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_debug_ibl: a null pointer");
+    if (n == 0u) return BRMI_OK;
+    return brmi::launch_debug_ibl(p, *env, environmentIndex, normals, albedo, metallicRoughness, coat, emissive, fuzz, viewWS, outDiffuse, outSpecular, n, static_cast<hipStream_t>(stream));
+}
 int brmi_debug_sample_grad(const brmi_scene_buffers* scene, const uint32_t* maxAnisotropy, uint32_t textureIndex, uint32_t samplerIndex, uint32_t uniformBinding, const float* uv, const float* ddx,
                            const float* ddy, float* outRGBA, uint32_t n, brmi_stream stream) {
     if (!scene || !uv || !ddx || !ddy || !outRGBA || (scene->textureCount && !scene->textures) || (scene->samplerCount && !scene->samplers)) return BRMI_ERR_INVALID;

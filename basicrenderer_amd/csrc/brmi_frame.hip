@@ -23,9 +23,12 @@ namespace brmi {
 //   frameConst[0] = mul(view, projection)           frameConst[1] = mul(view, unjitteredProjection)
 //   frameConst[2] = mul(prevView, prevUnjitteredProjection)
 //   objConst[o]   = { mul(model, cullCam.viewProjection), mul(model, frameConst[0]), mul(model, cullCam.viewZ) }
-BRMI_DEV void job_object_constants(const brmi_scene_buffers& sc, m4* frameConst, float* objConst, FrameSnapshot* snap, const float* bandPlanes, uint32_t o) {
+BRMI_DEV void job_object_constants(const brmi_scene_buffers& sc, m4* frameConst, float* objConst, FrameSnapshot* snap, const float* bandPlanes, const brmi_environment_info* environment, uint32_t o) {
     const uint32_t viewId = sc.perFrame->mainCameraIndex;
     if (o < 64u) {      // the job's first workgroup: the camera and the per-frame record the shading half will read (FrameSnapshot)
+        // ... and the frame's environment (brmi_set_environment; null without one): irradianceSH's coefficients folded once, with the shader's operations
+        if (environment && o < 27u) snap->envSH[o] = fold_sh_coefficient(environment, o);
+        if (environment && o == 27u) snap->envSH[27] = as_f32(environment->prefilteredCubemapDescriptorIndex);
         const uint32_t* pfSrc = reinterpret_cast<const uint32_t*>(sc.perFrame); uint32_t* pfDst = reinterpret_cast<uint32_t*>(&snap->perFrame);
         for (uint32_t i = o; i < sizeof(brmi_per_frame) / 4u; i += 64u) pfDst[i] = (i == offsetof(brmi_per_frame, mainCameraIndex) / 4u) ? 0u : pfSrc[i];
         const uint32_t* cSrc = reinterpret_cast<const uint32_t*>(sc.cameras + viewId); uint32_t* cDst = reinterpret_cast<uint32_t*>(&snap->camera);
@@ -240,11 +243,12 @@ struct FrameJobs {
     float sliceStart[64];        // first view depth of every light-cluster slice (brmi_update), [0] = 0, [gz + 1] = +inf
     uint4* frameState; uint64_t frameState16;      // brmi_execute: the culling pass's counters + survivor bitmasks, zeroed here (job 7)
     uint32_t firstBlock[8];      // block ranges of the seven jobs
+    const brmi_environment_info* environment;      // brmi_set_environment: the record perFrame.activeEnvironmentIndex names (null: no environment bound)
 };
 
 __global__ void __launch_bounds__(64) k_frame_constants(FrameJobs j) {
     const uint32_t b = blockIdx.x;
-    if (b < j.firstBlock[1]) job_object_constants(j.sc, j.frameConst, j.objConst, j.snapshot, j.bandPlanes, (b - j.firstBlock[0]) * 64u + threadIdx.x);
+    if (b < j.firstBlock[1]) job_object_constants(j.sc, j.frameConst, j.objConst, j.snapshot, j.bandPlanes, j.environment, (b - j.firstBlock[0]) * 64u + threadIdx.x);
     else if (b < j.firstBlock[2]) job_material_words(j.sc, j.matWords, j.alphaMats, (b - j.firstBlock[1]) * 64u + threadIdx.x);
     else if (b < j.firstBlock[3]) job_material_constants(j.sc, j.matConst, (b - j.firstBlock[2]) * 64u + threadIdx.x);
     else if (b < j.firstBlock[4]) job_shade_tables(j.sc, j.tables, j.W, j.H, j.stripes, j.sliceStart, (b - j.firstBlock[3]) * 64u + threadIdx.x);
@@ -280,6 +284,11 @@ int ensure_frame_constants(brmi_pass* p, hipStream_t s) {
     j.W = p->cfg.width; j.H = p->cfg.height; j.stripes = p->stripes;
     for (int k = 0; k < 3; k++) { j.bandPlanes[k] = p->bandPlaneTop[k]; j.bandPlanes[4 + k] = p->bandPlaneBottom[k]; }
     j.bandPlanes[3] = j.bandPlanes[7] = 0.0f;
+    j.environment = nullptr;
+    if (p->env.on) {
+        if (p->pfHost.activeEnvironmentIndex >= p->env.b.environmentCount) return fail(p, BRMI_ERR_INVALID, "perFrame.activeEnvironmentIndex (%u) exceeds the environment table (%u)", p->pfHost.activeEnvironmentIndex, p->env.b.environmentCount);
+        j.environment = p->env.b.environments + p->pfHost.activeEnvironmentIndex;
+    }
     for (uint32_t k = 0; k < 64; k++) j.sliceStart[k] = k < p->sliceStartHost.size() ? p->sliceStartHost[k] : 0.0f;
     auto blocks = [](uint32_t n) { return (std::max(1u, n) + 63u) / 64u; };
     j.lutF = p->wsPtr<float>(p->ws.lutF); j.shadeRows = p->wsPtr<ShadeRows>(p->ws.shadeRows); j.shadeAvgs = p->wsPtr<ShadeAverages>(p->ws.shadeAvgs); j.ggxQuads = p->wsPtr<GgxQuad>(p->ws.ggxQuads);

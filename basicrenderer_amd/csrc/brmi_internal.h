@@ -275,7 +275,9 @@ inline StreamScratchLayout stream_scratch_layout(uint32_t groupCount) {
 // THESE, never the caller's buffers: with frames in flight the host rewrites its camera buffer for frame k + n while frame k is still being
 // shaded on the other stream; the constants kernel of the pass's next frame runs behind the frameDone wait, so the copy is stable for as
 // long as anything reads it.  perFrame.mainCameraIndex of the copy is 0 (the copy holds that one camera).
-struct FrameSnapshot { brmi_per_frame perFrame; brmi_camera camera; };
+// envSH: with an environment bound (brmi_set_environment), the frame's environment as the shading pass reads it: the 27 coefficients of irradianceSH folded to
+// floats, then the bits of its prefilteredCubemapDescriptorIndex.
+struct FrameSnapshot { brmi_per_frame perFrame; brmi_camera camera; float envSH[28]; };
 
 struct LayerUniform { unsigned long long coatWord, fuzzWord, coatFilledWord, fuzzFilledWord; uint32_t coatUniform, fuzzUniform, coatFilled, fuzzFilled; };
 
@@ -409,6 +411,7 @@ struct brmi_pass {
     brmi::Workspace ws{};
     struct { bool on = false; brmi_streaming_buffers b{}; uint32_t groupCount = 0, activeGroupScanCount = 0; } streaming;      // brmi_set_streaming (cleared by brmi_set_scene)
     struct { bool on = false; brmi_debug_view_buffers b{}; } debugView;      // brmi_set_debug_view
+    struct { bool on = false; brmi_environment_buffers b{}; } env;      // brmi_set_environment (kept by brmi_set_scene: nothing of it depends on the scene)
     const uint32_t* samplerAniso = nullptr;      // brmi_set_sampler_anisotropy: device words, one per sampler of the scene (cleared by brmi_set_scene)
     brmi_camera camHost{};
     brmi_per_frame pfHost{};
@@ -457,6 +460,9 @@ bool debug_view_mode_built(uint32_t mode);                  // brmi_debugview.hi
 int launch_debug_view(brmi_pass* p, hipStream_t s);
 int launch_debug_sample_grad(const brmi_scene_buffers& sc, const uint32_t* maxAnisotropy, uint32_t textureIndex, uint32_t samplerIndex, bool uniformBinding, const float* uv, const float* ddx, const float* ddy,
                              float* outRGBA, uint32_t n, hipStream_t s);
+int launch_debug_ibl_lookup(const brmi_environment_buffers& env, uint32_t cubemap, const float* dirs, const float* lods, float* outRGBA, uint32_t n, hipStream_t s);
+int launch_debug_ibl(brmi_pass* p, const brmi_environment_buffers& env, uint32_t environmentIndex, const float* normals, const uint32_t* albedo, const uint32_t* metallicRoughness, const uint64_t* coat,
+                     const uint64_t* emissive, const uint64_t* fuzz, const float* viewWS, float* outDiffuse, float* outSpecular, uint32_t n, hipStream_t s);
 inline StreamArgs stream_args_of(const brmi_pass* p) {
     if (!p->streaming.on) return StreamArgs{nullptr, nullptr, nullptr, 0u, 0u};
     const StreamScratchLayout l = stream_scratch_layout(p->streaming.groupCount);

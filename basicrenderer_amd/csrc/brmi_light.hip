@@ -17,6 +17,7 @@
 //   * OpenPBR lookup tables are injected R16_UNORM / float tables, bilinearly filtered in fp32.
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "brmi_device.h"
 #include "brmi_internal.h"
@@ -52,9 +53,9 @@ __global__ void __launch_bounds__(256) k_lc_fill(ClusterArgs a) { lc_fill_block(
 #define BRMI_SHADE_WAVES_ALONE 5
 #endif
 static_assert(BRMI_SHADE_WAVES_ALONE != BRMI_SHADE_WAVES, "the two variants of k_shade<0> are told apart by their waves per SIMD");
-template <int MODE, int WAVES = BRMI_SHADE_WAVES>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE != 0 ? 1 : WAVES, 8)))
-k_shade(ShadeArgs a) {
+// (the body of k_shade and k_shade_ibl: IBL = the environment term, shade_pixel)
+template <int MODE, int WAVES, bool IBL>
+BRMI_DEV void shade_kernel(const ShadeArgs& a) {
     constexpr bool ALONE = WAVES == BRMI_SHADE_WAVES_ALONE;
     // The variant that shares the chip holds 136 registers per wave ON PURPOSE (round 5: the arithmetic needs 123): three of its waves then leave a SIMD
     // 104 registers for the other frame's geometry waves, four waves of 128 leave none -- the shading half gets faster and the frame slower (DESIGN.md 4.6:
@@ -106,7 +107,7 @@ k_shade(ShadeArgs a) {
             const uint64_t tileBase = (uint64_t)(firstTile + t) << 6;
             uint32_t ls = lane;
             if (ALONE) asm volatile("" : "+v"(ls));
-            const uint32_t cls = shade_pixel<0, ALONE ? BRMI_SHADE_STASH_ALONE : 0>(a, k, sliceStart, unormT, camK, cur, ok, tileBase, ls);
+            const uint32_t cls = shade_pixel<0, ALONE ? BRMI_SHADE_STASH_ALONE : 0, IBL>(a, k, sliceStart, unormT, camK, cur, ok, tileBase, ls);
             shade_defer(a, t, cls, ls);
             if (ALONE) nxt = fetch(nt, ntx, nty, nok);      // (the stand-alone variant: the next tile's words requested behind this tile's shading, ~14 registers less in it)
             cur = nxt; ok = nok; t = nt; tx = ntx; ty = nty;
@@ -140,10 +141,19 @@ k_shade(ShadeArgs a) {
                 px = (tile % a.tilesX) * 8u + (within >> 3); py = (tile / a.tilesX) * 8u + (within & 7u);
                 raw = load_raw_pixel(a, i, px, py);
             }
-            shade_pixel<MODE>(a, k, sliceStart, unormT, camK, raw, ok, i & ~63ull, (uint32_t)(i & 63ull));
+            shade_pixel<MODE, 0, IBL>(a, k, sliceStart, unormT, camK, raw, ok, i & ~63ull, (uint32_t)(i & 63ull));
         }
     }
 }
+template <int MODE, int WAVES = BRMI_SHADE_WAVES>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE != 0 ? 1 : WAVES, 8)))
+k_shade(ShadeArgs a) { shade_kernel<MODE, WAVES, false>(a); }
+// With an environment bound (brmi_set_environment): the same kernels with evaluateIBL in front of the light loop, under names of their own -- a pass without an
+// environment launches k_shade as it always did.  The register budgets are k_shade's but for the stand-alone plain variant, which is compiled for four waves
+// per SIMD: under five the cube lookup's temporaries spill 16 registers to scratch (profiles/ibl_resources.md).
+template <int MODE, int WAVES = BRMI_SHADE_WAVES>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE != 0 ? 1 : (WAVES == BRMI_SHADE_WAVES_ALONE ? 4 : WAVES), 8)))
+k_shade_ibl(ShadeArgs a) { shade_kernel<MODE, WAVES, true>(a); }
 
 __global__ void __launch_bounds__(256) k_expand_luts(const uint16_t* odE, const uint16_t* odAvg, const uint16_t* imE, const uint16_t* imAvg, float* out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -209,6 +219,7 @@ ShadeArgs shade_args_of(brmi_pass* p) {
     a.deferredWord = (p->shadeSerial & 1u) ? STRIPE_DEFERRED_B : STRIPE_DEFERRED_A;
     a.nextDeferredWord = (p->shadeSerial & 1u) ? STRIPE_DEFERRED_A : STRIPE_DEFERRED_B;
     a.stripeCapacity = p->deferredStripeCapacity;
+    a.envSH = p->wsPtr<FrameSnapshot>(p->ws.frameSnapshot)->envSH; a.envCubemaps = p->env.b.cubemaps; a.envCubemapCount = p->env.b.cubemapCount; a.envSpecular = p->env.b.specularIBL ? 1u : 0u;
     return a;
 }
 
@@ -240,6 +251,16 @@ static int launch_shade_range(brmi_pass* p, hipStream_t s, uint32_t row0, uint32
     // 8192 workgroups of four waves, four tiles per wave at 4K: against 4096 (eight tiles per wave) the kernel's tail is shorter (233 -> 226 us)
     // and, with another frame's geometry half in flight beside it, slots come free twice as often for that half's high-priority launches
     // (Bistro 4K, two frames in flight: 0.436 -> 0.413 ms per frame; 16384: 0.425, 2048: 0.49)
+    // a bound environment (brmi_set_environment) selects the k_shade_ibl instantiations; without one the launches are the ones they always were
+    if (p->env.on) {
+        if (p->shadeSharesChip) hipLaunchKernelGGL((k_shade_ibl<0, BRMI_SHADE_WAVES>), dim3(std::max(256u, p->shadeGridShared / share)), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_shade_ibl<0, BRMI_SHADE_WAVES_ALONE>), dim3(std::max(256u, 8192u / share)), dim3(256), 0, s, a);
+        if (p->sceneHasCoat) hipLaunchKernelGGL(k_shade_ibl<1>, dim3(512), dim3(256), 0, s, a);
+        if (p->sceneHasFuzz) hipLaunchKernelGGL(k_shade_ibl<2>, dim3(512), dim3(256), 0, s, a);
+        if (p->sceneHasCoat && p->sceneHasFuzz) hipLaunchKernelGGL(k_shade_ibl<3>, dim3(512), dim3(256), 0, s, a);
+        BRMI_LAUNCH_CHECK(p, "k_shade_ibl");
+        return BRMI_OK;
+    }
     if (p->shadeSharesChip) hipLaunchKernelGGL((k_shade<0, BRMI_SHADE_WAVES>), dim3(std::max(256u, p->shadeGridShared / share)), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((k_shade<0, BRMI_SHADE_WAVES_ALONE>), dim3(std::max(256u, 8192u / share)), dim3(256), 0, s, a);
     // deferred pixels by class: coat, fuzz, both -- only the variants some material of the scene can need
@@ -247,6 +268,64 @@ static int launch_shade_range(brmi_pass* p, hipStream_t s, uint32_t row0, uint32
     if (p->sceneHasFuzz) hipLaunchKernelGGL(k_shade<2>, dim3(512), dim3(256), 0, s, a);
     if (p->sceneHasCoat && p->sceneHasFuzz) hipLaunchKernelGGL(k_shade<3>, dim3(512), dim3(256), 0, s, a);
     BRMI_LAUNCH_CHECK(p, "k_shade");
+    return BRMI_OK;
+}
+
+// brmi_debug_ibl_lookup: the cube lookup as k_shade_ibl calls it, one lane per sample
+__global__ void __launch_bounds__(256) k_debug_ibl_lookup(const brmi_texture_desc* cubemaps, uint32_t cubemapCount, uint32_t cubemap, const float* dirs, const float* lods, float4* out, uint32_t n) {
+    __shared__ float texelTables[512];
+    stage_texel_tables(texelTables, nullptr, threadIdx.x, 256u); __syncthreads();
+    TexelTables tb; tb.t = texelTables;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f4 r = sample_cube_level(tb, cubemaps, cubemapCount, cubemap, f3{dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]}, lods[i]);
+    out[i] = make_float4(r.x, r.y, r.z, r.w);
+}
+int launch_debug_ibl_lookup(const brmi_environment_buffers& env, uint32_t cubemap, const float* dirs, const float* lods, float* outRGBA, uint32_t n, hipStream_t s) {
+    hipLaunchKernelGGL(k_debug_ibl_lookup, dim3((n + 255u) / 256u), dim3(256), 0, s, env.cubemaps, env.cubemapCount, cubemap, dirs, lods, reinterpret_cast<float4*>(outRGBA), n);
+    return hipGetLastError() == hipSuccess ? BRMI_OK : BRMI_ERR_HIP;
+}
+// brmi_debug_ibl: build_fragment + evaluate_ibl of made-up pixels, one per lane, each through the instantiation of its class (as the four k_shade_ibl do);
+// the environment's coefficients are folded into LDS with k_frame_constants' function
+struct DebugIblArgs { const brmi_environment_info* environment; const float3* viewWS; float* outDiffuse; float* outSpecular; uint32_t n; };
+__global__ void __launch_bounds__(256) k_debug_ibl(ShadeArgs a, DebugIblArgs d) {
+    const ShadeFrame k = make_shade_frame(a);
+    __shared__ float unormT[256];
+    __shared__ float sh[28];
+    unormT[threadIdx.x] = k.L.unorm8[threadIdx.x];
+    if (threadIdx.x < 27u) sh[threadIdx.x] = fold_sh_coefficient(d.environment, threadIdx.x);
+    __syncthreads();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= d.n) return;
+    RawPixel raw = empty_raw_pixel();
+    raw.ns = a.normals[i]; raw.al = a.albedo[i]; raw.mr = a.metallicRoughness[i]; raw.cs = a.coat[i]; raw.es = a.emissive[i]; raw.fs = a.fuzz[i];
+    const f3 V{d.viewWS[i].x, d.viewWS[i].y, d.viewWS[i].z};
+    Frag f; PixelCtx ctx;
+    f.coatWeight = satq(half_at(raw.cs, 3)); f.fuzzWeight = satq(unormT[raw.mr >> 24]);
+    const uint32_t cls = (f.coatWeight != 0.0f ? 1u : 0u) | (f.fuzzWeight != 0.0f ? 2u : 0u);
+    TexelTables tb; tb.t = unormT;
+    const IblEnv env{a.envCubemaps, a.envCubemapCount, d.environment->prefilteredCubemapDescriptorIndex, a.envSpecular};
+    f3 Fd{0.0f, 0.0f, 0.0f}, Fr{0.0f, 0.0f, 0.0f};
+    auto term = [&](auto mode) {
+        constexpr int MODE = decltype(mode)::value;
+        build_fragment<MODE>(a, k, unormT, raw, f3{0.0f, 0.0f, 0.0f}, V, f, ctx);
+        evaluate_ibl<MODE>(k.L, tb, (const float*)sh, env, f, ctx, a.ggxQuads, (raw.mr >> 8) & 0xFFu, unormT[raw.al >> 24], unormT[(raw.mr >> 8) & 0xFFu], unormT[(raw.mr >> 16) & 0xFFu], Fd, Fr);
+    };
+    if (cls == 0u) term(std::integral_constant<int, 0>{}); else if (cls == 1u) term(std::integral_constant<int, 1>{});
+    else if (cls == 2u) term(std::integral_constant<int, 2>{}); else term(std::integral_constant<int, 3>{});
+    d.outDiffuse[3 * i] = Fd.x; d.outDiffuse[3 * i + 1] = Fd.y; d.outDiffuse[3 * i + 2] = Fd.z;
+    d.outSpecular[3 * i] = Fr.x; d.outSpecular[3 * i + 1] = Fr.y; d.outSpecular[3 * i + 2] = Fr.z;
+}
+int launch_debug_ibl(brmi_pass* p, const brmi_environment_buffers& env, uint32_t environmentIndex, const float* normals, const uint32_t* albedo, const uint32_t* metallicRoughness, const uint64_t* coat,
+                     const uint64_t* emissive, const uint64_t* fuzz, const float* viewWS, float* outDiffuse, float* outSpecular, uint32_t n, hipStream_t s) {
+    if (int rc = ensure_frame_constants(p, s)) return rc;
+    ShadeArgs a = shade_args_of(p);
+    a.normals = reinterpret_cast<const float4*>(normals); a.albedo = albedo; a.metallicRoughness = metallicRoughness;
+    a.coat = reinterpret_cast<const unsigned long long*>(coat); a.emissive = reinterpret_cast<const unsigned long long*>(emissive); a.fuzz = reinterpret_cast<const unsigned long long*>(fuzz);
+    a.envCubemaps = env.cubemaps; a.envCubemapCount = env.cubemapCount; a.envSpecular = env.specularIBL ? 1u : 0u;
+    const DebugIblArgs d{env.environments + environmentIndex, reinterpret_cast<const float3*>(viewWS), outDiffuse, outSpecular, n};
+    hipLaunchKernelGGL(k_debug_ibl, dim3((n + 255u) / 256u), dim3(256), 0, s, a, d);
+    BRMI_LAUNCH_CHECK(p, "k_debug_ibl");
     return BRMI_OK;
 }
 

@@ -6,6 +6,7 @@
 #include "brmi_device.h"
 #include "brmi_internal.h"
 #include "brmi_shade_math.h"
+#include "brmi_texture.h"
 
 namespace brmi {
 
@@ -175,6 +176,9 @@ struct ShadeArgs {
     // 130 k tiles = 1.4 ms when most pixels carry coat or fuzz).
     uint32_t deferredWord, nextDeferredWord;   // word inside a stripe: this call's list length / the next call's (cleared here)
     uint32_t stripeCapacity;
+    // image-based lighting (brmi_set_environment), read by the k_shade_ibl instantiations alone.  envSH: the frame's environment as k_frame_constants folded it
+    // (FrameSnapshot::envSH: nine RGB coefficients of irradianceSH, then the bits of its prefilteredCubemapDescriptorIndex)
+    const float* envSH; const brmi_texture_desc* envCubemaps; uint32_t envCubemapCount, envSpecular;
 };
 
 BRMI_DEV float half_at(unsigned long long v, int k) { return f16_bits_to_f32((uint32_t)(v >> (16 * k)) & 0xFFFFu); }
@@ -377,6 +381,145 @@ BRMI_DEV f3 light_contribution(const Luts& L, const Frag& f, const PixelCtx& c, 
     return fma3v(brdf, lightColorIntensity * (attenuation * spotAtt * NoL), acc);      // the pixel's sum so far + this light
 }
 
+// =================================== image-based lighting =======================
+// evaluateIBL (IBL.hlsli:683-740) and what it calls, for one pixel whose Frag / PixelCtx are built.  The inputs are GetFragmentInfoScreenSpace's
+// (utilities.hlsli:2639-2709): diffuseAO = albedo.a (GTAO off), bentNormal = normalWS (lightFragment passes the normal twice), reflectedWS = reflect(-V, N) of
+// the adjusted normal, NdotV = max(MIN_N_DOT_V, N.V) of the STORED normal (f.NdotV, not the direct lights' saturate(dot(N, V)) of the adjusted one).
+// The direction of the cube lookups is correctly rounded fp32 without contraction (it picks a face and texels); the BRDF algebra holds the HDR tolerance like
+// the direct term's (hardware reciprocal, folded table rows, the per-code GGX fit).
+// A layer that is absent contributes exactly nothing, so the variants without it skip its terms (the argument the emissive term already rests on):
+//   * no fuzz (weight exactly 0): OpenPBRFuzzIncomingReflected = saturate(saturate(0) * finite) = 0, so fuzzIncomingScale = 1 - 0 = 1 and
+//     fuzzFr = 0 * saturate(color) * radiance = 0 for a finite radiance (texels are UNORM codes);
+//   * no coat (weight exactly 0): presence = 0 fails `presence > 0`, coatFr = 0; OpenPBRCoatBaseLayerScaleIncoming = passage * (1 - reflected) * extra with
+//     passage = 1 or lerp(1, finite, 0) = 1, reflected = saturate(0 * finite) = 0, extra = lerp(1, saturate(finite), 0 * darkening) = 1: exactly (1, 1, 1).
+template <typename ShPtr>
+BRMI_DEV f3 irradiance_sh(ShPtr sh, f3 n) {      // irradianceSH (IBL.hlsli:8-23): the basis in the order y, z, x as written, summed left to right
+    auto K = [&](int i) { return f3{sh[3 * i], sh[3 * i + 1], sh[3 * i + 2]}; };
+    return K(0) + K(1) * n.y + K(2) * n.z + K(3) * n.x + K(4) * n.y * n.x + K(5) * n.y * n.z + K(6) * (3.0f * n.z * n.z - 1.0f) + K(7) * n.z * n.x + K(8) * (n.x * n.x - n.y * n.y);
+}
+BRMI_DEV f3 gtao_multi_bounce(float visibility, f3 albedo) {      // gtaoMultiBounce (IBL.hlsli:30-38)
+    BRMI_FP_FAST
+    const f3 a = 2.0404f * albedo - f3{0.3324f, 0.3324f, 0.3324f}, b = -4.7951f * albedo + f3{0.6417f, 0.6417f, 0.6417f}, c = 2.7552f * albedo + f3{0.6903f, 0.6903f, 0.6903f};
+    const f3 v{visibility, visibility, visibility};
+    return max3v(v, ((v * a + b) * v + c) * v);
+}
+// computeSpecularAO (IBL.hlsli:63-72): SPECULAR_AMBIENT_OCCLUSION and SPECULAR_AO_SIMPLE are defined nowhere in the reference, so the `#if` at :65 compares 0
+// with 0 and SpecularAO_Lagarde (:54-58) is what compiles.  pow(x, y) = exp2(y * log2 x), as DXC lowers it (x = NoV + visibility >= MIN_N_DOT_V > 0).
+BRMI_DEV float specular_ao_lagarde(float NoV, float visibility, float roughness) {
+    return satq(__builtin_amdgcn_exp2f(__builtin_amdgcn_exp2f(-16.0f * roughness - 1.0f) * __builtin_amdgcn_logf(NoV + visibility)) - 1.0f + visibility);
+}
+BRMI_DEV void ggx_dir_albedo_q(const GgxQuad& g, float x, float& A, float& B) {      // mx_ggx_dir_albedo_analytic's (A, B) from the per-code quadratics
+    BRMI_FP_FAST
+    float r[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) r[i] = g.q0[i] + x * (g.q1[i] + x * g.q2[i]);
+    A = clampf(qdiv(r[0], r[2]), 0.0f, 1.0f); B = clampf(qdiv(r[1], r[3]), 0.0f, 1.0f);
+}
+struct IblEnv { const brmi_texture_desc* cubemaps; uint32_t cubemapCount, cubemap, specular; };
+// Fd and Fr + coatFr + fuzzFr (the reference's diffuseIBL / specularIBL).  sh: the environment's folded coefficients (any address space);
+// tb: the code / 255 table in LDS; ao, pr, coatR: the pixel's UNORM values albedo.a, metallicRoughness.y, .z.
+template <int MODE, typename ShPtr>
+BRMI_DEV void evaluate_ibl(const Luts& L, const TexelTables& tb, ShPtr sh, const IblEnv& env, const Frag& f, const PixelCtx& c, const GgxQuad* quads, uint32_t roughCode, float ao, float pr, float coatR, f3& Fd, f3& FrSum) {
+    const BaseState& base = c.base;
+    const float NdotV = f.NdotV;
+    const f3 N = f.normalWS;
+    const float perceptualRoughness = clampf(pr, BRMI_MIN_PERCEPTUAL_ROUGHNESS, 1.0f), coatPerceptualRoughness = clampf(coatR, BRMI_MIN_PERCEPTUAL_ROUGHNESS, 1.0f);
+    // reflect(-V, N) = i - 2 * N * dot(i, N); getReflectedVector = lerp(r, n, roughness * roughness) with the roughness alpha (IBL.hlsli:74-83)
+    const f3 inc = -f.viewWS;
+    const f3 reflected = inc - 2.0f * N * dot3(inc, N);
+    const f3 r = lerp3(reflected, N, f.roughness * f.roughness);
+    const float levels = (float)(BRMI_IBL_PREFILTER_LEVELS - 1u);
+    f3 specularRadiance{0.0f, 0.0f, 0.0f}, fuzzRadiance{0.0f, 0.0f, 0.0f};
+    if (env.specular) {       // PSO_SPECULAR_IBL (wave-uniform)
+        specularRadiance = xyz(sample_cube_level(tb, env.cubemaps, env.cubemapCount, env.cubemap, r, perceptualRoughness * levels));
+        if (MODE & 2) fuzzRadiance = xyz(sample_cube_level(tb, env.cubemaps, env.cubemapCount, env.cubemap, r, f.fuzzRoughness * levels));
+    }
+    const f3 diffuseIrradiance = max3v(irradiance_sh(sh, normalize3_q(N + N)), f3{0.0f, 0.0f, 0.0f}) * (1.0f / PI_F);
+    // EvaluateOpenPBRBaseLayerIBL (IBL.hlsli:553-566)
+    const float averageComplement = lut_od_avg(L, base.weightedSpecularIor, base.specularAlpha);
+    const float cachedView = max2(0.0f, qdiv(sample_folded_row(c.odRow, NdotV), max2(averageComplement, 1.0e-12f)));
+    const float diffuseEnergyComp = max2(0.0f, cachedView * averageComplement);
+    const float diffuseDirectionalAlbedo = fon_dir_albedo(NdotV, base.baseDiffuseRoughness);
+    float A, B; ggx_dir_albedo_q(quads[roughCode], NdotV, A, B);
+    const f3 dielectricE = base.dielectricSpecularF0 * A + f3{B, B, B}, metalE = base.metalSpecularF0 * A + f3{B, B, B};
+    const float metalMultipleScatter = sample_folded_row(c.imRow, NdotV);
+    Fd = base.diffuseColor * diffuseIrradiance * diffuseDirectionalAlbedo * diffuseEnergyComp * ao;
+    f3 Fr = (base.dielectricSpecularWeight * dielectricE + base.metalSpecularWeight * metalE + base.metalMultipleScatterScale * metalMultipleScatter) * specularRadiance;
+    const float fuzzViewReflected = (MODE & 2) ? fuzz_incoming_reflected(L, f.fuzzWeight, f.fuzzRoughness, NdotV) : 0.0f;
+    const float fuzzIncomingScale = 1.0f - fuzzViewReflected;
+    f3 coatViewAttenuation{1.0f, 1.0f, 1.0f}, coatFr{0.0f, 0.0f, 0.0f};
+    if (MODE & 1) {
+        coatViewAttenuation = coat_scale_incoming(L, c.coat, NdotV);
+        if (env.specular && c.coat.presence > 0.0f)
+            coatFr = xyz(sample_cube_level(tb, env.cubemaps, env.cubemapCount, env.cubemap, r, coatPerceptualRoughness * levels)) * coat_reflected(L, c.coat, NdotV);
+    }
+    f3 fuzzFr = (MODE & 2) ? fuzzViewReflected * satq3(f.fuzzColor) * fuzzRadiance : f3{0.0f, 0.0f, 0.0f};      // OpenPBRFuzzSheenIBL (IBL.hlsli:242-246)
+    const f3 baseAttenuation = f3{fuzzIncomingScale, fuzzIncomingScale, fuzzIncomingScale} * coatViewAttenuation;
+    Fd = Fd * baseAttenuation; Fr = Fr * baseAttenuation; coatFr = coatFr * fuzzIncomingScale;
+    Fd = Fd * gtao_multi_bounce(ao, base.diffuseColor);
+    if (env.specular) {
+        const float specularAO = specular_ao_lagarde(NdotV, ao, f.roughness);
+        Fr = Fr * gtao_multi_bounce(specularAO, base.dielectricSpecularF0);
+        if (MODE & 1) coatFr = coatFr * gtao_multi_bounce(specularAO, f.coatF0);
+        if (MODE & 2) fuzzFr = fuzzFr * gtao_multi_bounce(specularAO, f.fuzzColor);
+    }
+    FrSum = Fr + coatFr + fuzzFr;
+}
+
+// GetFragmentInfoScreenSpace + PopulateFragmentInfoFromOpenPBR + the light-independent part of the BRDF for one pixel whose class is MODE (f.coatWeight and
+// f.fuzzWeight are the caller's: they decide the class).  viewDir: the unit vector towards the eye, correctly rounded.
+template <int MODE>
+BRMI_DEV void build_fragment(const ShadeArgs& a, const ShadeFrame& k, const float* unorm8, const RawPixel& raw, f3 posWS, f3 viewDir, Frag& f, PixelCtx& ctx) {
+    const Luts& L = k.L;
+    const uint32_t al = raw.al, mr = raw.mr;
+    const unsigned long long cs = raw.cs, es = raw.es, fs = raw.fs;
+    f.posWS = posWS; f.viewWS = viewDir;
+    const float4 ns = raw.ns;
+    const f3 nrm{ns.x, ns.y, ns.z};
+    // code / 255 from the LDS copy of the table: seven reads per pixel that do not go through the vector-memory path
+    const f3 baseColor{unorm8[al & 0xFFu], unorm8[(al >> 8) & 0xFFu], unorm8[(al >> 16) & 0xFFu]};
+    const float metal = unorm8[mr & 0xFFu], pr = unorm8[(mr >> 8) & 0xFFu], coatR = unorm8[(mr >> 16) & 0xFFu];
+    const float prc = clampf(pr, BRMI_MIN_PERCEPTUAL_ROUGHNESS, 1.0f);
+    f.roughness = prc * prc;
+    const float NdotVraw = dot3(nrm, viewDir);
+    f.normalWS = normalize3_q(nrm + max2(0.0f, -NdotVraw + BRMI_MIN_N_DOT_V) * viewDir);      // (N too: N.L and N.V carry its absolute error to terms that vanish with them)
+    f.NdotV = max2(BRMI_MIN_N_DOT_V, NdotVraw);
+    uint32_t opIndex = (uint32_t)(ns.w + 0.5f);
+    if (opIndex >= a.openpbrMaterialCount) opIndex = 0;
+    const MatConst mc = a.matConst[opIndex];
+    const float baseWeight = mc.baseWeight, specularWeight = mc.specularWeight;
+    const f3 specularColor{mc.specR, mc.specG, mc.specB};
+    const f3 weightedBaseColor = satq3(baseColor * baseWeight);
+    f.dielectricSpecularF0 = f3{mc.dielF0[0], mc.dielF0[1], mc.dielF0[2]};      // sat(specularColor * dielF0Scalar), per material (k_frame_constants)
+    const float coatPR = clampf(coatR, BRMI_MIN_PERCEPTUAL_ROUGHNESS, 1.0f);
+    f.dielectricSpecularWeight = satq(1.0f - metal);
+    f.metalSpecularWeight = satq(metal * specularWeight);
+    f.metalSpecularF0 = f3{0.0f, 0.0f, 0.0f}; f.metalAverageFresnel = f3{0.0f, 0.0f, 0.0f};
+    // every use of the metal lobe's inputs is multiplied by the metal weight: a dielectric pixel (weight exactly 0) skips them
+    if (f.metalSpecularWeight != 0.0f) {
+        f.metalSpecularF0 = satq3(weightedBaseColor * specularColor);
+        const f3 safeF0 = satq3(weightedBaseColor), wmF0 = f3{1.0f, 1.0f, 1.0f} - safeF0;
+        const float cosMax = 1.0f / 7.0f;
+        const f3 wmF0b = f3{1.0f, 1.0f, 1.0f} - satq3(safeF0), wmTint = f3{1.0f, 1.0f, 1.0f} - satq3(specularColor);
+        const f3 num = (satq3(safeF0) + wmF0b * k.om5) * wmTint;
+        const float den = cosMax * k.om6;
+        const f3 b = num * qrcp(max2(den, 1.0e-6f));
+        f.metalAverageFresnel = satq3(safeF0 + wmF0 * (1.0f / 21.0f) - b * (1.0f / 126.0f));
+    }
+    f.albedo = weightedBaseColor;
+    f.emissive = f3{half_at(es, 0), half_at(es, 1), half_at(es, 2)};
+    f.coatColor = satq3(f3{half_at(cs, 0), half_at(cs, 1), half_at(cs, 2)});
+    f.coatRoughness = coatPR * coatPR;
+    f.coatF0 = satq3(f.coatColor * mc.coatF0Scalar);
+    f.coatIor = mc.coatIor; f.coatDarkening = mc.coatDarkening;
+    f.fuzzColor = satq3(f3{half_at(fs, 0), half_at(fs, 1), half_at(fs, 2)}); f.fuzzRoughness = satq(half_at(fs, 3));
+    f.baseDiffuseRoughness = mc.baseDiffuseRoughness;
+    f.specularAlpha = f.roughness; f.weightedSpecularIor = mc.weightedSpecularIor;
+    f.diffuseColor = weightedBaseColor * (1.0f - metal);
+    const uint32_t entry = opIndex * 256u + ((mr >> 8) & 0xFFu);
+    ctx = make_pixel_ctx<MODE>(L, f, a.shadeRows + entry, a.shadeAvgs[entry], mc, a.ggxQuads, (mr >> 8) & 0xFFu, (mr >> 16) & 0xFFu);
+}
+
 // One pixel per lane of DeferredCSMain (deferred.hlsl:11-106).  Every lane of the wave runs through here together -- `live` lanes
 // shade, the others (no geometry, outside the band, another material class) only lend a hand where the wave works as a team:
 //   * the lights of a cluster are STAGED one per lane (a lane loads the 64 B record of one light of the list: all records of a
@@ -388,7 +531,9 @@ BRMI_DEV f3 light_contribution(const Luts& L, const Frag& f, const PixelCtx& c, 
 // MODE = class of pixel this instantiation shades (0 plain, 1 coat, 2 fuzz, 3 both: a layer that is absent has factors of exactly
 // 1 / 0, so the plain variant needs half the registers -- the same idea as the reference's per-material-permutation pixel lists).
 // Returns, for a live lane whose class is not MODE, that class (MODE 0 defers such pixels); 0 otherwise.
-template <int MODE, int STASH = 0>      // STASH: floats of the metal lobe's inputs parked in LDS (0, 6 or 9)
+// IBL: an environment is bound (brmi_set_environment): evaluateIBL is the first addend of the pixel's lighting, before the light loop, as in lightFragment
+// (lighting.hlsli:406-438); instantiations of their own (k_shade_ibl), so that a pass without an environment runs the kernels it always ran.
+template <int MODE, int STASH = 0, bool IBL = false>      // STASH: floats of the metal lobe's inputs parked in LDS (0, 6 or 9)
 BRMI_DEV uint32_t shade_pixel(const ShadeArgs& a, const ShadeFrame& k, const float* sliceStart, const float* unorm8, const float4* camK, const RawPixel& raw, bool live, uint64_t tileBase, uint32_t within) {
     const Luts& L = k.L;
     const uint32_t gx = k.gx, gy = k.gy, gz = k.gz, nearSlices = k.nearSlices;
@@ -396,11 +541,12 @@ BRMI_DEV uint32_t shade_pixel(const ShadeArgs& a, const ShadeFrame& k, const flo
     const float* stash = &metalStash[0][STASH ? threadIdx.x : 0u];
     live = live && as_u32(raw.d) != BRMI_DEPTH_EMPTY_BITS;
     Frag f; PixelCtx ctx; f3 posWS, posVS;        // only read by lanes that stay `live` (no initialiser: nothing to materialise for the others)
+    f3 environmentTerm{0.0f, 0.0f, 0.0f};
     uint32_t opaqueZero = 0u;
     asm volatile("" : "+v"(opaqueZero));            // the LDS reads of the camera constants stay inside this call (hoisted out of the tile loop they pin 27 registers)
     uint32_t ci = 0xFFFFFFFFu, cls = 0u;
-    const uint32_t al = raw.al, mr = raw.mr;
-    const unsigned long long cs = raw.cs, es = raw.es, fs = raw.fs;
+    const uint32_t mr = raw.mr;
+    const unsigned long long cs = raw.cs;
     // ---- class of the pixel, its position and its light cluster: what the light staging waits for
     if (live) {
         f.coatWeight = satq(half_at(cs, 3)); f.fuzzWeight = satq(unorm8[mr >> 24]);
@@ -453,51 +599,7 @@ BRMI_DEV uint32_t shade_pixel(const ShadeArgs& a, const ShadeFrame& k, const flo
         // (V stays correctly rounded on both paths: the bent normal below is nrm + k V, which cancels to a vector of length ~1e-4 where the stored normal points
         // away from the eye, and an ulp of V is then a part in a thousand of N -- measured: 205 fp16 ulps on such pixels with a fast V)
         const f3 viewDir = normalize3_q(toEye);
-        f.posWS = posWS; f.viewWS = viewDir;
-        const float4 ns = raw.ns;
-        const f3 nrm{ns.x, ns.y, ns.z};
-        // code / 255 from the LDS copy of the table: seven reads per pixel that do not go through the vector-memory path
-        const f3 baseColor{unorm8[al & 0xFFu], unorm8[(al >> 8) & 0xFFu], unorm8[(al >> 16) & 0xFFu]};
-        const float metal = unorm8[mr & 0xFFu], pr = unorm8[(mr >> 8) & 0xFFu], coatR = unorm8[(mr >> 16) & 0xFFu];
-        const float prc = clampf(pr, BRMI_MIN_PERCEPTUAL_ROUGHNESS, 1.0f);
-        f.roughness = prc * prc;
-        const float NdotVraw = dot3(nrm, viewDir);
-        f.normalWS = normalize3_q(nrm + max2(0.0f, -NdotVraw + BRMI_MIN_N_DOT_V) * viewDir);      // (N too: N.L and N.V carry its absolute error to terms that vanish with them)
-        f.NdotV = max2(BRMI_MIN_N_DOT_V, NdotVraw);
-        uint32_t opIndex = (uint32_t)(ns.w + 0.5f);
-        if (opIndex >= a.openpbrMaterialCount) opIndex = 0;
-        const MatConst mc = a.matConst[opIndex];
-        const float baseWeight = mc.baseWeight, specularWeight = mc.specularWeight;
-        const f3 specularColor{mc.specR, mc.specG, mc.specB};
-        const f3 weightedBaseColor = satq3(baseColor * baseWeight);
-        f.dielectricSpecularF0 = f3{mc.dielF0[0], mc.dielF0[1], mc.dielF0[2]};      // sat(specularColor * dielF0Scalar), per material (k_frame_constants)
-        const float coatPR = clampf(coatR, BRMI_MIN_PERCEPTUAL_ROUGHNESS, 1.0f);
-        f.dielectricSpecularWeight = satq(1.0f - metal);
-        f.metalSpecularWeight = satq(metal * specularWeight);
-        f.metalSpecularF0 = f3{0.0f, 0.0f, 0.0f}; f.metalAverageFresnel = f3{0.0f, 0.0f, 0.0f};
-        // every use of the metal lobe's inputs is multiplied by the metal weight: a dielectric pixel (weight exactly 0) skips them
-        if (f.metalSpecularWeight != 0.0f) {
-            f.metalSpecularF0 = satq3(weightedBaseColor * specularColor);
-            const f3 safeF0 = satq3(weightedBaseColor), wmF0 = f3{1.0f, 1.0f, 1.0f} - safeF0;
-            const float cosMax = 1.0f / 7.0f;
-            const f3 wmF0b = f3{1.0f, 1.0f, 1.0f} - satq3(safeF0), wmTint = f3{1.0f, 1.0f, 1.0f} - satq3(specularColor);
-            const f3 num = (satq3(safeF0) + wmF0b * k.om5) * wmTint;
-            const float den = cosMax * k.om6;
-            const f3 b = num * qrcp(max2(den, 1.0e-6f));
-            f.metalAverageFresnel = satq3(safeF0 + wmF0 * (1.0f / 21.0f) - b * (1.0f / 126.0f));
-        }
-        f.albedo = weightedBaseColor;
-        f.emissive = f3{half_at(es, 0), half_at(es, 1), half_at(es, 2)};
-        f.coatColor = satq3(f3{half_at(cs, 0), half_at(cs, 1), half_at(cs, 2)});
-        f.coatRoughness = coatPR * coatPR;
-        f.coatF0 = satq3(f.coatColor * mc.coatF0Scalar);
-        f.coatIor = mc.coatIor; f.coatDarkening = mc.coatDarkening;
-        f.fuzzColor = satq3(f3{half_at(fs, 0), half_at(fs, 1), half_at(fs, 2)}); f.fuzzRoughness = satq(half_at(fs, 3));
-        f.baseDiffuseRoughness = mc.baseDiffuseRoughness;
-        f.specularAlpha = f.roughness; f.weightedSpecularIor = mc.weightedSpecularIor;
-        f.diffuseColor = weightedBaseColor * (1.0f - metal);
-        const uint32_t entry = opIndex * 256u + ((mr >> 8) & 0xFFu);
-        ctx = make_pixel_ctx<MODE>(L, f, a.shadeRows + entry, a.shadeAvgs[entry], mc, a.ggxQuads, (mr >> 8) & 0xFFu, (mr >> 16) & 0xFFu);
+        build_fragment<MODE>(a, k, unorm8, raw, posWS, viewDir, f, ctx);
         if (STASH && f.metalSpecularWeight != 0.0f) {
             metalStash[0][threadIdx.x] = ctx.base.metalSpecularF0.x; metalStash[1][threadIdx.x] = ctx.base.metalSpecularF0.y; metalStash[2][threadIdx.x] = ctx.base.metalSpecularF0.z;
             metalStash[3][threadIdx.x] = ctx.base.metalMultipleScatterScale.x; metalStash[4][threadIdx.x] = ctx.base.metalMultipleScatterScale.y; metalStash[5][threadIdx.x] = ctx.base.metalMultipleScatterScale.z;
@@ -508,8 +610,16 @@ BRMI_DEV uint32_t shade_pixel(const ShadeArgs& a, const ShadeFrame& k, const flo
             metalStash[9 % S][threadIdx.x] = f.emissive.x; metalStash[10 % S][threadIdx.x] = f.emissive.y; metalStash[11 % S][threadIdx.x] = f.emissive.z;
             metalStash[12 % S][threadIdx.x] = ctx.fonA; metalStash[13 % S][threadIdx.x] = ctx.fonK0; metalStash[14 % S][threadIdx.x] = ctx.fonK1; metalStash[15 % S][threadIdx.x] = ctx.fonK2; metalStash[16 % S][threadIdx.x] = ctx.fonK3;
         }
+        if (IBL) {
+            TexelTables tb; tb.t = unorm8;
+            const IblEnv env{a.envCubemaps, a.envCubemapCount, as_u32(kconst(a.envSH)[27]), a.envSpecular};
+            f3 Fd, Fr;
+            evaluate_ibl<MODE>(L, tb, kconst(a.envSH), env, f, ctx, a.ggxQuads, (mr >> 8) & 0xFFu, unorm8[raw.al >> 24], unorm8[(mr >> 8) & 0xFFu], unorm8[(mr >> 16) & 0xFFu], Fd, Fr);
+            environmentTerm = Fd + Fr;       // combineDiffuseAndSpecular: color += Fd + Fr, color = 0
+        }
     }
     f3 lighting{0.0f, 0.0f, 0.0f};
+    if (IBL) lighting = environmentTerm;
     // Waterfall over the distinct clusters of the wave (an 8x8 tile usually sits in one).  The loop and the staging run with every lane
     // of the wave; only the light loop proper is restricted to the lanes of the cluster.  The lane set comes from a ballot and `uci`
     // depends on the loop-carried mask, so neither can be replaced by the per-lane `ci`.

@@ -214,6 +214,9 @@ BRMI_DEV float average_fresnel(float eta) {
     return 0.997118f + 0.1014f * s - 0.965241f * s2 - 0.130607f * s2 * s;
 }
 
+// One of the 27 coefficients of irradianceSH (IBL.hlsli:8-23) as the shader evaluates it: SH_FLOAT_SCALE_INVERSE is the unparenthesised `1.0f / SH_FLOAT_SCALE`,
+// so int * scale * SH_FLOAT_SCALE_INVERSE is ((int * scale) * 1.0f) / 100.  Folded once per frame (k_frame_constants), read by k_shade_ibl.
+BRMI_DEV float fold_sh_coefficient(const brmi_environment_info* e, uint32_t i) { return (((float)e->sphericalHarmonics[i] * e->sphericalHarmonicsScale) * 1.0f) / (float)BRMI_SH_FLOAT_SCALE; }
 
 // What the shading pass needs from (OpenPBR material, 8-bit perceptual roughness code) alone.  For such a pair the opaque-dielectric
 // energy complement is a function of the cosine only: lut_od_e's bilinear fetch in each of the two IOR slices, the lerp between the

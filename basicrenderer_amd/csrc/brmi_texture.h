@@ -232,6 +232,43 @@ BRMI_DEV f4 sample_level(const TexelTables& tb, const TexBinding& tx, f2 uv, flo
     return sample_prepared(tb, tx, prepare_level(tx, lodIn), uv);
 }
 
+// TextureCube::SampleLevel(g_linearClamp, dir, lod) ("cube lookup"): the face of the major axis (X if |x| >= |y| && |x| >= |z|, else Y if
+// |y| >= |z|, else Z; the major component's sign picks + or -), the face coordinates of the Direct3D cube layout, then the 2D sampler above on that face
+// alone -- linear min / mag / mip, clamp addressing, the lod clamped to the chain.  No filtering across face edges (hardware filters seamlessly there: the
+// definition's stated gap).  Every step IEEE fp32, the two divisions correctly rounded.  A direction that is all zero or not finite reads face 0 at (0.5, 0.5).
+struct CubeCoord { uint32_t face; f2 uv; };
+BRMI_DEV CubeCoord cube_face_uv(f3 d) {
+    const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
+    const float big = 3.4028234e38f;
+    if (!(ax <= big && ay <= big && az <= big) || (ax == 0.0f && ay == 0.0f && az == 0.0f)) return {0u, {0.5f, 0.5f}};
+    uint32_t face; float sc, tc, ma;
+    if (ax >= ay && ax >= az) { ma = ax; face = d.x < 0.0f ? 1u : 0u; sc = d.x < 0.0f ? d.z : -d.z; tc = -d.y; }
+    else if (ay >= az) { ma = ay; face = d.y < 0.0f ? 3u : 2u; sc = d.x; tc = d.y < 0.0f ? -d.z : d.z; }
+    else { ma = az; face = d.z < 0.0f ? 5u : 4u; sc = d.z < 0.0f ? -d.x : d.x; tc = -d.y; }
+    return {face, {(sc / ma + 1.0f) * 0.5f, (tc / ma + 1.0f) * 0.5f}};
+}
+// one face of a cubemap as the 2D sampler sees it (g_linearClamp).  A descriptor without texels, size or levels is unbound; the format is taken as
+// BRMI_TEXTURE_FORMAT_RGBA8_UNORM whatever the descriptor says (the table is caller-owned device memory: brmi_set_environment states the contract)
+template <typename TexPtr>
+BRMI_DEV TexBinding bind_cube_face(TexPtr faces, uint32_t face) {
+    TexBinding b{};
+    const auto* td = faces + face;
+    b.texels = reinterpret_cast<const uint32_t*>(td->texels); b.mipOffset = (const uint32_t*)td->mipOffset;
+    b.width = td->width; b.height = td->height; b.mipCount = td->mipCount; b.srgb = false;
+    b.bound = b.texels != nullptr && b.width != 0u && b.height != 0u && b.mipCount != 0u && b.mipCount <= BRMI_TEXTURE_MAX_MIPS;
+    b.sm.addressU = BRMI_ADDRESS_CLAMP; b.sm.addressV = BRMI_ADDRESS_CLAMP; b.sm.minFilter = BRMI_FILTER_LINEAR; b.sm.magFilter = BRMI_FILTER_LINEAR; b.sm.mipFilter = BRMI_FILTER_LINEAR;
+    b.sm.mipLodBias = 0.0f; b.sm.minLod = 0.0f; b.sm.maxLod = 3.4028234e38f;
+    return b;
+}
+// `cubemaps`: the table of brmi_environment_buffers (six descriptors per cubemap); a cubemap the table does not hold and an unbound face read as zero
+BRMI_DEV f4 sample_cube_level(const TexelTables& tb, const brmi_texture_desc* cubemaps, uint32_t cubemapCount, uint32_t cubemap, f3 dir, float lod) {
+    if (cubemaps == nullptr || cubemap >= cubemapCount) return {0.0f, 0.0f, 0.0f, 0.0f};
+    const CubeCoord c = cube_face_uv(dir);
+    const TexBinding b = bind_cube_face(cubemaps + (size_t)cubemap * 6u, c.face);
+    if (!b.bound) return {0.0f, 0.0f, 0.0f, 0.0f};
+    return sample_level(tb, b, c.uv, lod);
+}
+
 BRMI_DEV float log2_poly(float x) {
     const uint32_t b = as_u32(x);
     const int e = (int)((b >> 23) & 0xFFu) - 127;

@@ -76,6 +76,7 @@ class VisibilityRenderer:
         self.device_arrays = dict(scene.device_arrays)      # this pass's own copies (two passes in flight each have their camera buffers)
         self._check(self.lib.brmi_set_scene(self._h, C.byref(self.sb)), "brmi_set_scene")
         self._anisotropy = None      # set_anisotropy's table
+        self._environment, self._environment_index = None, 0      # set_environment's device tables, perFrame.activeEnvironmentIndex of this pass's frames
         self._debug_mode, self._debug_view, self._pf_own = 0, None, None      # set_debug_view: outputType, the targets, this pass's per-frame record
         self._frame_index = 0        # of the last brmi_update
         self.descs = {}
@@ -141,10 +142,11 @@ class VisibilityRenderer:
         """The scene's per-frame record; with a debug view set, this pass's own copy of it with perFrame.outputType filled in (scenes are shared)."""
         pf = src.per_frame_host()
         mode = self._debug_mode
-        if not mode:
+        if not mode and not self._environment_index:
             return pf
         self._pf_own = np.array(pf, copy=True)
         self._pf_own.view(np.uint32)[capi.PER_FRAME_OUTPUT_TYPE_WORD] = mode
+        self._pf_own.view(np.uint32)[capi.PER_FRAME_ACTIVE_ENVIRONMENT_WORD] = self._environment_index
         return self._pf_own
 
     def update(self, frame_index=0):
@@ -366,6 +368,58 @@ class VisibilityRenderer:
         self._check(self.lib.brmi_set_sampler_anisotropy(self._h, table.data_ptr(), capi.u32(count)), "brmi_set_sampler_anisotropy")
         self._anisotropy = table
 
+    # -- image-based lighting (brmi_set_environment) ------------------------------------------------
+    def environment_buffers(self, environments, specular=True):
+        """(capi.EnvironmentBuffers, tensors to keep alive) for a list of environment.Environment: the tables uploaded to this pass's device."""
+        from . import environment as envmod
+        torch, keep = self.torch, []
+
+        def up(a):
+            t = torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(self.device)
+            keep.append(t)
+            return t.data_ptr()
+        info, descs, _ = envmod.environment_tables(environments, up)
+        b = capi.EnvironmentBuffers()
+        b.structSize, b.specularIBL = C.sizeof(capi.EnvironmentBuffers), 1 if specular else 0
+        b.environments, b.environmentCount = up(info), len(environments)
+        b.cubemaps, b.cubemapCount = up(descs), len(environments)
+        return b, keep
+
+    def set_environment(self, env, index=0, specular=True):
+        """Image-based lighting from the next frame on: an environment.Environment or a list of them (perFrame.activeEnvironmentIndex = `index` picks the
+        frame's), or None for off -- exactly the frames of a pass that never called this.  The tables are this pass's own tensors; replacing or dropping
+        them waits for the device first (a frame in flight may be reading them).  Repeats the last update() with the index in this pass's per-frame record."""
+        if self._environment is not None:
+            self.torch.cuda.synchronize(self.device)
+        if env is None:
+            self._check(self.lib.brmi_set_environment(self._h, None), "brmi_set_environment")
+            self._environment, self._environment_index = None, 0
+        else:
+            envs = list(env) if isinstance(env, (list, tuple)) else [env]
+            b, keep = self.environment_buffers(envs, specular)
+            self._check(self.lib.brmi_set_environment(self._h, None), "brmi_set_environment")
+            self._environment_index = int(index)
+            self.update(self._frame_index)      # the index first: the binding is refused while the last update names an entry the table lacks
+            self._check(self.lib.brmi_set_environment(self._h, C.byref(b)), "brmi_set_environment")
+            self._environment = dict(buffers=b, keep=keep)
+        # the device record too (brmi_frame_update::perFrameHost is by contract the host copy of that buffer)
+        pf = self.device_arrays["perFrame"]
+        words = self.torch.from_numpy(np.array([self._environment_index], dtype=np.int32)).to(self.device)
+        pf.view(self.torch.int32)[capi.PER_FRAME_ACTIVE_ENVIRONMENT_WORD: capi.PER_FRAME_ACTIVE_ENVIRONMENT_WORD + 1].copy_(words)
+        self.update(self._frame_index)
+
+    def set_environment_index(self, index):
+        """perFrame.activeEnvironmentIndex of the frames from the next update() on (which this repeats); an index the bound table lacks makes it raise."""
+        previous, self._environment_index = self._environment_index, int(index)
+        try:
+            self.update(self._frame_index)
+        except BrmiError:
+            self._environment_index = previous
+            raise
+        pf = self.device_arrays["perFrame"]
+        words = self.torch.from_numpy(np.array([self._environment_index], dtype=np.int32)).to(self.device)
+        pf.view(self.torch.int32)[capi.PER_FRAME_ACTIVE_ENVIRONMENT_WORD: capi.PER_FRAME_ACTIVE_ENVIRONMENT_WORD + 1].copy_(words)
+
     # -- debug views (brmi_set_debug_view, perFrame.outputType) ------------------------------------
     def set_debug_view(self, mode, fill=0, check=True):
         """The debug view of the frames from the next update() on: a perFrame.outputType number or the reference's name without the OUTPUT_ prefix
@@ -454,6 +508,7 @@ class VisibilityRenderer:
             # every byte the pass used is caller-owned: drop the resource tensors and the uploaded scene with the pass
             self.res = {}
             self._debug_view = None
+            self._environment = None
             self._scene_keep = []
             self.device_arrays = {}
             if hasattr(self.scene, "device_arrays"):

@@ -283,6 +283,26 @@ int brmi_set_streaming(brmi_pass* pass, const brmi_streaming_buffers* streaming)
  * Call after brmi_set_scene (which forgets the binding).  BRMI_ERR_INVALID: count != the scene's samplerCount. */
 int brmi_set_sampler_anisotropy(brmi_pass* pass, const uint32_t* maxAnisotropy, uint32_t count);
 
+/* Image-based lighting: with an environment bound the shading pass adds evaluateIBL (BR/shaders/Include/IBL.hlsli:683-740) as the first addend of
+ * a pixel's lighting, in fp32 inside the shading kernel, as lightFragment does under PSO_IMAGE_BASED_LIGHTING.  The environment of a frame is
+ * perFrameHost->activeEnvironmentIndex of that frame's brmi_update.  prefilteredCubemapDescriptorIndex indexes `cubemaps` in whole cubemaps; a TextureCube's
+ * SampleLevel(g_linearClamp, dir, lod) is the software definition of DESIGN.md 2 (major axis, the 2D sampler on that face, no filtering across face edges).
+ * All memory is caller-owned DEVICE memory that every frame reads and none owns (the rule of brmi_execute_split for lights and materials).
+ * NULL switches it off and gives exactly the frames -- kernels, bytes -- of a pass that never called it.  brmi_set_scene does NOT forget this binding: nothing of
+ * it depends on the scene.
+ * Refused with BRMI_ERR_INVALID before anything is launched: a wrong structSize, a null table with a non-zero count, environmentCount == 0, and (here and at
+ * brmi_update) an activeEnvironmentIndex >= environmentCount.  What the host cannot see is the caller's contract: the six faces of a cubemap are square, of one
+ * size, mipCount and BRMI_TEXTURE_FORMAT_RGBA8_UNORM, every chain inside its allocation.  The kernel reads each face by that face's own descriptor, clamps texel
+ * coordinates and levels to it, and reads a cubemap index >= cubemapCount or a descriptor without texels, size or levels (or with more than
+ * BRMI_TEXTURE_MAX_MIPS) as zero radiance: it never faults on a table that disagrees with itself. */
+typedef struct brmi_environment_buffers {
+    uint32_t structSize;
+    uint32_t specularIBL;                        /* PSO_SPECULAR_IBL: the reference defines it whenever screen-space reflections are off (PSOManager.cpp:1908-1913) */
+    const brmi_environment_info* environments;   uint32_t environmentCount;   /* Builtin::Environment::InfoBuffer, device */
+    const brmi_texture_desc*     cubemaps;       uint32_t cubemapCount;       /* device; cubemap c = entries 6c .. 6c+5 in the order +X -X +Y -Y +Z -Z */
+} brmi_environment_buffers;
+int brmi_set_environment(brmi_pass* pass, const brmi_environment_buffers* env);
+
 /* Debug views.  brmi_set_debug_view binds the targets (NULL unbinds and gives exactly the frames of a pass that never called it); with a target bound and
  * perFrame.outputType != 0, brmi_execute / brmi_execute_split run brmi_debug_view behind the shading stage (on the shading stream); an outputType the stage
  * would refuse makes them fail BEFORE anything is launched.  The lit HDR frame and
@@ -392,6 +412,21 @@ int brmi_debug_arith_in_range(const float* a, float* outRcp, float* outSqrt, flo
 int brmi_debug_sample_grad(const brmi_scene_buffers* scene, const uint32_t* maxAnisotropy /* device, or NULL */, uint32_t textureIndex,
                            uint32_t samplerIndex, uint32_t uniformBinding, const float* uv, const float* ddx, const float* ddy, float* outRGBA,
                            uint32_t n, brmi_stream stream);
+
+/* The shading pass's environment term on device data, one lane per sample, through the device functions k_shade_ibl calls.  Every pointer
+ * but `env` (a host struct of device pointers, as brmi_set_environment takes it) is a device pointer.
+ * brmi_debug_ibl_lookup: the cube lookup alone.  directions: n float3, lods: n floats, outRGBA: n float4 = SampleLevel(g_linearClamp, direction, lod) of cubemap
+ *   `cubemapIndex` of env->cubemaps.
+ * brmi_debug_ibl: the whole term of n made-up pixels.  The G-buffer words are those a RawPixel holds (normals: n float4 with the OpenPBR record's index in w;
+ *   albedo / metallicRoughness: n packed UNORM words; coat / emissive / fuzz: n words of four halves), viewWS: n float3, the unit vector towards the eye.  The
+ *   OpenPBR records, lookup tables and per-material shading tables are those of `pass` (after brmi_setup and a brmi_update: the call builds the frame constants
+ *   if the pass has not yet), the environment is entry `environmentIndex` of `env`, which need not be bound to the pass.  outDiffuse / outSpecular: n float3
+ *   each, fp32: Fd and Fr + coatFr + fuzzFr, the reference's diffuseIBL / specularIBL split. */
+int brmi_debug_ibl_lookup(const brmi_environment_buffers* env, uint32_t cubemapIndex, const float* directions, const float* lods, float* outRGBA, uint32_t n,
+                          brmi_stream stream);
+int brmi_debug_ibl(brmi_pass* pass, const brmi_environment_buffers* env, uint32_t environmentIndex, const float* normals, const uint32_t* albedo,
+                   const uint32_t* metallicRoughness, const uint64_t* coat, const uint64_t* emissive, const uint64_t* fuzz, const float* viewWS,
+                   float* outDiffuse, float* outSpecular, uint32_t n, brmi_stream stream);
 
 #ifdef __cplusplus
 }

@@ -422,6 +422,21 @@ typedef struct brmi_sampler_desc {
     float    mipLodBias, minLod, maxLod;
 } brmi_sampler_desc;                        /* 32 B */
 
+/* ---- image-based lighting -----------------------------------------------------------------
+ * EnvironmentInfo, BR/include/ShaderBuffers.h:453-459 / BR/shaders/Include/structs.hlsli:627-633, byte for byte.  The 27 integers are nine RGB
+ * coefficients of irradianceSH (BR/shaders/Include/IBL.hlsli:8-23: basis 1, y, z, x, yx, yz, 3z^2 - 1, zx, x^2 - y^2), each worth
+ * value * sphericalHarmonicsScale / BRMI_SH_FLOAT_SCALE.  prefilteredCubemapDescriptorIndex counts whole cubemaps of
+ * brmi_environment_buffers::cubemaps (brmi.h); cubeMapDescriptorIndex (the skybox) is not read. */
+#define BRMI_SH_FLOAT_SCALE 100                 /* BR/shaders/Include/constants.hlsli:6-7 */
+#define BRMI_IBL_PREFILTER_LEVELS 12u           /* prefilteredRadiance, IBL.hlsli:85-92: lod = roughness * (12 - 1) */
+typedef struct brmi_environment_info {
+    uint32_t cubeMapDescriptorIndex;
+    uint32_t prefilteredCubemapDescriptorIndex;
+    float    sphericalHarmonicsScale;
+    int32_t  sphericalHarmonics[27];
+    uint32_t pad[2];
+} brmi_environment_info;                    /* 128 B */
+
 /* ---- path-internal records --------------------------------------------------------------- */
 /* 16-byte packed visible cluster, BR/shaders/Include/visibleClusterPacking.hlsli:83-122,220-235
  *   x: view:8 | instance:24      y: localMeshlet:14 | group[17:0]:18
