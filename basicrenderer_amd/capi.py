@@ -139,7 +139,23 @@ class EnvironmentInfo(C.Structure):
 
 class EnvironmentBuffers(C.Structure):
     """brmi_environment_buffers (include/brmi.h): caller-owned device tables of the image-based lighting."""
+    _fields_ = [("structSize", u32), ("specularIBL", u32), ("environments", vp), ("environmentCount", u32), ("reserved0", u32), ("cubemaps", vp), ("cubemapCount", u32),
+                ("reserved1", u32), ("skybox", u32), ("reserved2", u32 * 3)]
+
+
+class EnvironmentBuffersV1(C.Structure):
+    """brmi_environment_buffers as it was before `skybox` (BRMI_ENVIRONMENT_BUFFERS_SIZE_V1 bytes): still accepted, and means skybox off."""
     _fields_ = [("structSize", u32), ("specularIBL", u32), ("environments", vp), ("environmentCount", u32), ("cubemaps", vp), ("cubemapCount", u32)]
+
+
+class TextureDesc(C.Structure):
+    """brmi_texture_desc (include/brmi_types.h), 96 B."""
+    _fields_ = [("texels", vp), ("width", u32), ("height", u32), ("mipCount", u32), ("format", u32), ("mipOffset", u32 * 16), ("reserved", u32 * 2)]
+
+
+TEXTURE_FORMAT_RGBA8_UNORM, TEXTURE_FORMAT_RGBA8_UNORM_SRGB, TEXTURE_FORMAT_RGBA16_FLOAT = 0, 1, 2      # BRMI_TEXTURE_FORMAT_*
+TEXTURE_MAX_MIPS = 16
+ENVIRONMENT_BUFFERS_SIZE_V1 = 40
 
 
 SH_FLOAT_SCALE = 100                      # BRMI_SH_FLOAT_SCALE
@@ -256,7 +272,8 @@ BRMI_EXPORTS = ["brmi_abi_version", "brmi_default_config", "brmi_create", "brmi_
                 "brmi_shade", "brmi_set_shade_slabs", "brmi_read_counters", "brmi_stage_times", "brmi_set_timed_stages", "brmi_algorithmic_bytes", "brmi_algorithmic_bytes_launched", "brmi_debug_arith", "brmi_debug_arith_in_range", "brmi_debug_read_bin_records", "brmi_debug_wide_triangles", "brmi_debug_lean_clusters", "brmi_debug_read_lean_queue", "brmi_debug_read_held",
                 "brmi_streaming_scratch_bytes", "brmi_set_streaming", "brmi_streaming_feedback", "brmi_set_sampler_anisotropy", "brmi_debug_sample_grad",
                 "brmi_abi_minor", "brmi_debug_view_bytes", "brmi_set_debug_view", "brmi_debug_view",
-                "brmi_set_environment", "brmi_debug_ibl_lookup", "brmi_debug_ibl"]
+                "brmi_set_environment", "brmi_debug_ibl_lookup", "brmi_debug_ibl",
+                "brmi_skybox", "brmi_env_convert", "brmi_env_project_sh", "brmi_env_prefilter", "brmi_env_build_bytes", "brmi_debug_env_lookup"]
 
 
 def brmi_lib():
@@ -316,5 +333,13 @@ def brmi_lib():
             lib.brmi_set_environment.argtypes = [vp, C.POINTER(EnvironmentBuffers)]
             lib.brmi_debug_ibl_lookup.argtypes = [C.POINTER(EnvironmentBuffers), u32, vp, vp, vp, u32, vp]
             lib.brmi_debug_ibl.argtypes = [vp, C.POINTER(EnvironmentBuffers), u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]
+        if hasattr(lib, "brmi_skybox"):
+            lib.brmi_skybox.argtypes = [vp, vp]
+            lib.brmi_env_convert.argtypes = [vp, vp, u32, u32, vp]
+            lib.brmi_env_project_sh.argtypes = [vp, u32, vp, u32, u32, u32, vp]
+            lib.brmi_env_prefilter.argtypes = [vp, vp, u32, u32, u32, vp]
+            lib.brmi_env_build_bytes.argtypes = [u32, u32, C.POINTER(u64), C.POINTER(u64)]
+            lib.brmi_env_build_bytes.restype = u64
+            lib.brmi_debug_env_lookup.argtypes = [vp, u32, u32, vp, vp, vp, u32, vp]
         _brmi_lib = lib
     return _brmi_lib

@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -769,17 +770,71 @@ int brmi_set_sampler_anisotropy(brmi_pass* p, const uint32_t* maxAnisotropy, uin
     p->samplerAniso = maxAnisotropy;
     return BRMI_OK;
 }
+// brmi_environment_buffers grew by `skybox`: the struct of either size is taken, the field is read only where structSize covers it
+static bool environment_struct_size_ok(uint32_t structSize) { return structSize == sizeof(brmi_environment_buffers) || structSize == BRMI_ENVIRONMENT_BUFFERS_SIZE_V1; }
+// the caller's struct of either size as the grown one: the first layout's fields, then `skybox` where structSize covers it (nothing past the caller's object is read)
+static brmi_environment_buffers environment_struct_of(const brmi_environment_buffers* e) {
+    brmi_environment_buffers b{};
+    b.structSize = (uint32_t)sizeof(b); b.specularIBL = e->specularIBL; b.environments = e->environments; b.environmentCount = e->environmentCount;
+    b.cubemaps = e->cubemaps; b.cubemapCount = e->cubemapCount;
+    b.skybox = e->structSize >= offsetof(brmi_environment_buffers, skybox) + sizeof(uint32_t) && e->skybox != 0u ? 1u : 0u;
+    return b;
+}
 int brmi_set_environment(brmi_pass* p, const brmi_environment_buffers* e) {
     if (!p) return BRMI_ERR_INVALID;
     if (!e) { if (p->env.on) p->updateSerial++; p->env.on = false; p->env.b = brmi_environment_buffers{}; return BRMI_OK; }
-    if (e->structSize != sizeof(brmi_environment_buffers)) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_environment: structSize %u, expected %zu", e->structSize, sizeof(brmi_environment_buffers));
+    if (!environment_struct_size_ok(e->structSize))
+        return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_environment: structSize %u, expected %zu (or %u, the struct before `skybox`)", e->structSize, sizeof(brmi_environment_buffers), BRMI_ENVIRONMENT_BUFFERS_SIZE_V1);
     if ((!e->environments && e->environmentCount) || (!e->cubemaps && e->cubemapCount)) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_environment: a null table with a non-zero count");
     if (e->environmentCount == 0u || !e->environments) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_environment: environmentCount is 0 (NULL unbinds)");
     if (p->updated && p->pfHost.activeEnvironmentIndex >= e->environmentCount)
         return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_environment: the last brmi_update's activeEnvironmentIndex is %u, the table has %u entries", p->pfHost.activeEnvironmentIndex, e->environmentCount);
-    p->env.b = *e; p->env.on = true;
+    p->env.b = environment_struct_of(e); p->env.on = true;
     p->updateSerial++;       // the frame constants fold the environment's coefficients: re-evaluated by the next stage call
     return BRMI_OK;
+}
+// what keeps the skybox stage from running, checked by the stage and by brmi_execute_split in front of a frame's first launch (as debug_view_refusal is)
+static int skybox_refusal(brmi_pass* p) {
+    if (!p->setupDone) return brmi::fail(p, BRMI_ERR_STATE, "brmi_skybox: call brmi_setup first");
+    if (!p->updated) return brmi::fail(p, BRMI_ERR_STATE, "brmi_skybox: call brmi_update first (the environment is perFrame.activeEnvironmentIndex of the last update)");
+    if (!p->env.on || !p->env.b.skybox) return brmi::fail(p, BRMI_ERR_STATE, "brmi_skybox: no environment with `skybox` set is bound (brmi_set_environment)");
+    if (!p->res[BRMI_RES_LINEAR_DEPTH] || !p->res[BRMI_RES_HDR_COLOR] || !p->res[BRMI_RES_GBUF_MOTION_VECTORS]) return brmi::fail(p, BRMI_ERR_STATE, "brmi_skybox: the depth, HDR or motion-vector surface is not bound");
+    return BRMI_OK;
+}
+int brmi_skybox(brmi_pass* p, brmi_stream stream) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (int rc = skybox_refusal(p)) return rc;
+    return brmi::launch_skybox(p, static_cast<hipStream_t>(stream));
+}
+
+// ---- environment build (brmi_envbuild.hip): every refusal comes before the first launch
+static bool env_size_ok(uint32_t size) { return size != 0u && size <= 16384u; }
+int brmi_env_convert(const brmi_texture_desc* equirect, const brmi_texture_desc* cube, uint32_t size, uint32_t cubeFormat, brmi_stream stream) {
+    if (!equirect || !cube || !env_size_ok(size) || cubeFormat != BRMI_TEXTURE_FORMAT_RGBA16_FLOAT) return BRMI_ERR_INVALID;
+    return brmi::launch_env_convert(equirect, cube, size, static_cast<hipStream_t>(stream));
+}
+int brmi_env_project_sh(const brmi_texture_desc* cubemaps, uint32_t cubemapCount, brmi_environment_info* environments, uint32_t environmentCount, uint32_t environmentIndex, uint32_t size, brmi_stream stream) {
+    if (!cubemaps || cubemapCount == 0u || !environments || environmentIndex >= environmentCount || !env_size_ok(size)) return BRMI_ERR_INVALID;
+    return brmi::launch_env_project_sh(cubemaps, cubemapCount, environments + environmentIndex, size, static_cast<hipStream_t>(stream));
+}
+int brmi_env_prefilter(const brmi_texture_desc* sourceCube, const brmi_texture_desc* prefiltered, uint32_t size, uint32_t levels, uint32_t prefilteredFormat, brmi_stream stream) {
+    if (!sourceCube || !prefiltered || !env_size_ok(size) || levels == 0u || levels > BRMI_TEXTURE_MAX_MIPS || prefilteredFormat != BRMI_TEXTURE_FORMAT_RGBA8_UNORM) return BRMI_ERR_INVALID;
+    return brmi::launch_env_prefilter(sourceCube, prefiltered, size, levels, static_cast<hipStream_t>(stream));
+}
+uint64_t brmi_env_build_bytes(uint32_t size, uint32_t levels, uint64_t* cubeBytes, uint64_t* prefilteredBytes) {
+    if (cubeBytes) *cubeBytes = 0; if (prefilteredBytes) *prefilteredBytes = 0;
+    if (!env_size_ok(size) || levels == 0u || levels > BRMI_TEXTURE_MAX_MIPS) return 0;
+    const uint64_t cube = 6ull * size * size * 8ull;
+    uint64_t chain = 0;
+    for (uint32_t m = 0; m < levels; m++) { const uint64_t s = std::max(1u, size >> m); chain += s * s; }
+    chain *= 6ull * 4ull;
+    if (cubeBytes) *cubeBytes = cube; if (prefilteredBytes) *prefilteredBytes = chain;
+    return cube + chain;
+}
+int brmi_debug_env_lookup(const brmi_texture_desc* cubemaps, uint32_t cubemapCount, uint32_t cubemapIndex, const float* directions, const float* lods, float* outRGBA, uint32_t n, brmi_stream stream) {
+    if (!cubemaps || !directions || !lods || !outRGBA) return BRMI_ERR_INVALID;
+    if (n == 0u) return BRMI_OK;
+    return brmi::launch_debug_env_lookup(cubemaps, cubemapCount, cubemapIndex, directions, lods, outRGBA, n, static_cast<hipStream_t>(stream));
 }
 int brmi_streaming_feedback(brmi_pass* p, brmi_stream stream) {
     CHECK_READY(p);
@@ -886,6 +941,8 @@ int brmi_execute_split(brmi_pass* p, brmi_stream stream, brmi_stream shadeStream
     // a debug view the pass cannot write is refused here, before the frame's first launch and before any of its bookkeeping
     const bool debugView = p->debugView.on && p->pfHost.outputType != BRMI_OUTPUT_COLOR;
     if (debugView && (rc = debug_view_refusal(p))) return rc;
+    const bool skybox = p->env.on && p->env.b.skybox;      // ... and so is a skybox stage that could not run
+    if (skybox && (rc = skybox_refusal(p))) return rc;
     p->executesSinceTimes++;
     const bool split = shadeStream != stream;
     p->splitFrame = split;
@@ -975,6 +1032,8 @@ int brmi_execute_split(brmi_pass* p, brmi_stream stream, brmi_stream shadeStream
     rc = brmi_shade(p, stream);
     p->shadeSharesChip = false;
     if (rc) return rc;
+    // SkyboxRenderPass behind the deferred shading (the reference's Deferred -> Skybox -> Forward), only where the bound environment asks for it
+    if (skybox && (rc = brmi_skybox(p, stream))) return rc;
     // the debug payload of perFrame.outputType, from the surfaces the frame has just made (behind the shading stage, on its stream, in front of the frame's end)
     if (debugView && (rc = brmi_debug_view(p, stream))) return rc;
     if (split) { BRMI_HIP(p, hipEventRecord(p->frameDone, static_cast<hipStream_t>(stream))); p->frameDoneRecorded = true; }
@@ -1153,18 +1212,18 @@ int brmi_debug_arith_in_range(const float* a, float* outRcp, float* outSqrt, flo
 }
 
 int brmi_debug_ibl_lookup(const brmi_environment_buffers* env, uint32_t cubemapIndex, const float* directions, const float* lods, float* outRGBA, uint32_t n, brmi_stream stream) {
-    if (!env || env->structSize != sizeof(brmi_environment_buffers) || !directions || !lods || !outRGBA) return BRMI_ERR_INVALID;
+    if (!env || !environment_struct_size_ok(env->structSize) || !directions || !lods || !outRGBA) return BRMI_ERR_INVALID;
     if (n == 0u) return BRMI_OK;
-    return brmi::launch_debug_ibl_lookup(*env, cubemapIndex, directions, lods, outRGBA, n, static_cast<hipStream_t>(stream));
+    return brmi::launch_debug_ibl_lookup(environment_struct_of(env), cubemapIndex, directions, lods, outRGBA, n, static_cast<hipStream_t>(stream));
 }
 int brmi_debug_ibl(brmi_pass* p, const brmi_environment_buffers* env, uint32_t environmentIndex, const float* normals, const uint32_t* albedo, const uint32_t* metallicRoughness, const uint64_t* coat,
                    const uint64_t* emissive, const uint64_t* fuzz, const float* viewWS, float* outDiffuse, float* outSpecular, uint32_t n, brmi_stream stream) {
     CHECK_READY(p);
-    if (!env || env->structSize != sizeof(brmi_environment_buffers) || !env->environments || environmentIndex >= env->environmentCount)
+    if (!env || !environment_struct_size_ok(env->structSize) || !env->environments || environmentIndex >= env->environmentCount)
         return brmi::fail(p, BRMI_ERR_INVALID, "brmi_debug_ibl: no such environment (structSize, table or index)");
     if (!normals || !albedo || !metallicRoughness || !coat || !emissive || !fuzz || !viewWS || !outDiffuse || !outSpecular) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_debug_ibl: a null pointer");
     if (n == 0u) return BRMI_OK;
-    return brmi::launch_debug_ibl(p, *env, environmentIndex, normals, albedo, metallicRoughness, coat, emissive, fuzz, viewWS, outDiffuse, outSpecular, n, static_cast<hipStream_t>(stream));
+    return brmi::launch_debug_ibl(p, environment_struct_of(env), environmentIndex, normals, albedo, metallicRoughness, coat, emissive, fuzz, viewWS, outDiffuse, outSpecular, n, static_cast<hipStream_t>(stream));
 }
 int brmi_debug_sample_grad(const brmi_scene_buffers* scene, const uint32_t* maxAnisotropy, uint32_t textureIndex, uint32_t samplerIndex, uint32_t uniformBinding, const float* uv, const float* ddx,
                            const float* ddy, float* outRGBA, uint32_t n, brmi_stream stream) {

@@ -463,6 +463,12 @@ int launch_debug_sample_grad(const brmi_scene_buffers& sc, const uint32_t* maxAn
 int launch_debug_ibl_lookup(const brmi_environment_buffers& env, uint32_t cubemap, const float* dirs, const float* lods, float* outRGBA, uint32_t n, hipStream_t s);
 int launch_debug_ibl(brmi_pass* p, const brmi_environment_buffers& env, uint32_t environmentIndex, const float* normals, const uint32_t* albedo, const uint32_t* metallicRoughness, const uint64_t* coat,
                      const uint64_t* emissive, const uint64_t* fuzz, const float* viewWS, float* outDiffuse, float* outSpecular, uint32_t n, hipStream_t s);
+// brmi_skybox.hip / brmi_envbuild.hip (the entry points have checked their arguments)
+int launch_skybox(brmi_pass* p, hipStream_t s);
+int launch_env_convert(const brmi_texture_desc* equirect, const brmi_texture_desc* cube, uint32_t size, hipStream_t s);
+int launch_env_project_sh(const brmi_texture_desc* cubemaps, uint32_t cubemapCount, brmi_environment_info* env, uint32_t size, hipStream_t s);
+int launch_env_prefilter(const brmi_texture_desc* source, const brmi_texture_desc* prefiltered, uint32_t size, uint32_t levels, hipStream_t s);
+int launch_debug_env_lookup(const brmi_texture_desc* cubemaps, uint32_t cubemapCount, uint32_t cubemap, const float* dirs, const float* lods, float* outRGBA, uint32_t n, hipStream_t s);
 inline StreamArgs stream_args_of(const brmi_pass* p) {
     if (!p->streaming.on) return StreamArgs{nullptr, nullptr, nullptr, 0u, 0u};
     const StreamScratchLayout l = stream_scratch_layout(p->streaming.groupCount);

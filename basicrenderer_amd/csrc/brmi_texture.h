@@ -269,6 +269,54 @@ BRMI_DEV f4 sample_cube_level(const TexelTables& tb, const brmi_texture_desc* cu
     return sample_level(tb, b, c.uv, lod);
 }
 
+// ---- BRMI_TEXTURE_FORMAT_RGBA16_FLOAT (the environment build and the skybox stage; nothing above reads it) ---------------------------------------------
+// The same sampler on 8 B texels of four halves: prepare_level's level choice, fetch_footprint's addresses and weights (clamp, the 2x2 footprint around
+// u * w - 0.5, or the single texel of a point filter), a + t * (b - a) along x then y; a half decodes to the float of the same value, exactly.
+// (the cubes these kernels read are never _SRGB: the UNORM half of the texel tables is all they stage)
+BRMI_DEV void stage_unorm_table(float* lds256, uint32_t tid, uint32_t nthreads) { for (uint32_t i = tid; i < 256u; i += nthreads) lds256[i] = (float)i / 255.0f; }
+typedef const __attribute__((address_space(1))) unsigned long long* GlobalTexels16;
+BRMI_DEV f4 decode_half4(unsigned long long t) {
+    const uint32_t lo = (uint32_t)t, hi = (uint32_t)(t >> 32);
+    return {f16_bits_to_f32(lo & 0xFFFFu), f16_bits_to_f32(lo >> 16), f16_bits_to_f32(hi & 0xFFFFu), f16_bits_to_f32(hi >> 16)};
+}
+BRMI_DEV f4 sample_footprint_f16(const TexBinding& tx, uint32_t levelOffset, uint32_t level, f2 uv, uint32_t filter) {
+    const int w = (int)(tx.width >> level ? tx.width >> level : 1u), h = (int)(tx.height >> level ? tx.height >> level : 1u);
+    GlobalTexels16 base = (GlobalTexels16)(reinterpret_cast<const unsigned long long*>(tx.texels) + levelOffset);
+    if (filter == BRMI_FILTER_POINT) {
+        const int x = address_texel(floor_to_int(uv.x * (float)w), w, tx.sm.addressU), y = address_texel(floor_to_int(uv.y * (float)h), h, tx.sm.addressV);
+        return decode_half4(base[(size_t)y * (size_t)w + (size_t)x]);
+    }
+    const float fx = uv.x * (float)w - 0.5f, fy = uv.y * (float)h - 0.5f;
+    const float tX = fx - floorf(fx), tY = fy - floorf(fy);
+    const int x0 = floor_to_int(fx), y0 = floor_to_int(fy);
+    const int xa = address_texel(x0, w, tx.sm.addressU), xb = address_texel(inc_sat(x0), w, tx.sm.addressU);
+    const int ya = address_texel(y0, h, tx.sm.addressV), yb = address_texel(inc_sat(y0), h, tx.sm.addressV);
+    const unsigned long long c00 = base[(size_t)ya * (size_t)w + (size_t)xa], c10 = base[(size_t)ya * (size_t)w + (size_t)xb];
+    const unsigned long long c01 = base[(size_t)yb * (size_t)w + (size_t)xa], c11 = base[(size_t)yb * (size_t)w + (size_t)xb];
+    return lerp4(lerp4(decode_half4(c00), decode_half4(c10), tX), lerp4(decode_half4(c01), decode_half4(c11), tX), tY);
+}
+BRMI_DEV f4 sample_level_f16(const TexBinding& tx, f2 uv, float lodIn) {
+    if (!tx.bound) return {1.0f, 1.0f, 1.0f, 1.0f};
+    const LevelSetup s = prepare_level(tx, lodIn);
+    const f4 a = sample_footprint_f16(tx, s.off0, s.l0, uv, s.filter);
+    if (s.frac == 0.0f) return a;
+    return lerp4(a, sample_footprint_f16(tx, s.off1, s.l1, uv, s.filter), s.frac);
+}
+// one 2D descriptor under g_linearClamp, whatever its format: RGBA16_FLOAT through the functions above, anything else through the RGBA8 path as it is
+template <typename TexPtr>
+BRMI_DEV f4 sample_desc_level_any(const TexelTables& tb, TexPtr desc, f2 uv, float lod) {
+    const TexBinding b = bind_cube_face(desc, 0u);
+    if (!b.bound) return {0.0f, 0.0f, 0.0f, 0.0f};
+    if (desc->format == BRMI_TEXTURE_FORMAT_RGBA16_FLOAT) return sample_level_f16(b, uv, lod);
+    return sample_level(tb, b, uv, lod);
+}
+// sample_cube_level for a cube of either format (each face by its own descriptor's format)
+BRMI_DEV f4 sample_cube_level_any(const TexelTables& tb, const brmi_texture_desc* cubemaps, uint32_t cubemapCount, uint32_t cubemap, f3 dir, float lod) {
+    if (cubemaps == nullptr || cubemap >= cubemapCount) return {0.0f, 0.0f, 0.0f, 0.0f};
+    const CubeCoord c = cube_face_uv(dir);
+    return sample_desc_level_any(tb, cubemaps + (size_t)cubemap * 6u + c.face, c.uv, lod);
+}
+
 BRMI_DEV float log2_poly(float x) {
     const uint32_t b = as_u32(x);
     const int e = (int)((b >> 23) & 0xFFu) - 127;

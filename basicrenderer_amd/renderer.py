@@ -369,8 +369,9 @@ class VisibilityRenderer:
         self._anisotropy = table
 
     # -- image-based lighting (brmi_set_environment) ------------------------------------------------
-    def environment_buffers(self, environments, specular=True):
-        """(capi.EnvironmentBuffers, tensors to keep alive) for a list of environment.Environment: the tables uploaded to this pass's device."""
+    def environment_buffers(self, environments, specular=True, skybox=False):
+        """(capi.EnvironmentBuffers, tensors to keep alive) for a list of environment.Environment: the tables uploaded to this pass's device.  An environment
+        with a sky cube (Environment.cube16) brings it as a cubemap of its own behind the prefiltered ones."""
         from . import environment as envmod
         torch, keep = self.torch, []
 
@@ -380,14 +381,18 @@ class VisibilityRenderer:
             return t.data_ptr()
         info, descs, _ = envmod.environment_tables(environments, up)
         b = capi.EnvironmentBuffers()
-        b.structSize, b.specularIBL = C.sizeof(capi.EnvironmentBuffers), 1 if specular else 0
+        # without the skybox switch the struct goes over as its first layout (the fields up to cubemapCount are where they were): a build of the library from
+        # before the switch (BRMI_LIB_PATH, A/B runs) takes it too
+        b.structSize, b.specularIBL = C.sizeof(capi.EnvironmentBuffers) if skybox else capi.ENVIRONMENT_BUFFERS_SIZE_V1, 1 if specular else 0
         b.environments, b.environmentCount = up(info), len(environments)
-        b.cubemaps, b.cubemapCount = up(descs), len(environments)
+        b.cubemaps, b.cubemapCount = up(descs), len(descs) // 6
+        b.skybox = 1 if skybox else 0
         return b, keep
 
-    def set_environment(self, env, index=0, specular=True):
+    def set_environment(self, env, index=0, specular=True, skybox=False):
         """Image-based lighting from the next frame on: an environment.Environment or a list of them (perFrame.activeEnvironmentIndex = `index` picks the
-        frame's), or None for off -- exactly the frames of a pass that never called this.  The tables are this pass's own tensors; replacing or dropping
+        frame's), or None for off -- exactly the frames of a pass that never called this.  skybox=True: the frame's pixels without geometry show the
+        environment's sky cube (brmi_skybox behind the shading stage); without it a frame launches what it always launched.  The tables are this pass's own tensors; replacing or dropping
         them waits for the device first (a frame in flight may be reading them).  Repeats the last update() with the index in this pass's per-frame record."""
         if self._environment is not None:
             self.torch.cuda.synchronize(self.device)
@@ -396,7 +401,7 @@ class VisibilityRenderer:
             self._environment, self._environment_index = None, 0
         else:
             envs = list(env) if isinstance(env, (list, tuple)) else [env]
-            b, keep = self.environment_buffers(envs, specular)
+            b, keep = self.environment_buffers(envs, specular, skybox)
             self._check(self.lib.brmi_set_environment(self._h, None), "brmi_set_environment")
             self._environment_index = int(index)
             self.update(self._frame_index)      # the index first: the binding is refused while the last update names an entry the table lacks

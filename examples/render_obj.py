@@ -34,7 +34,8 @@ def main():
     ap.add_argument("obj"); ap.add_argument("png")
     ap.add_argument("--size", default="1920x1080"); ap.add_argument("--lights", type=int, default=32); ap.add_argument("--features", type=int, default=0)
     ap.add_argument("--anisotropy", type=int, default=0, metavar="N", help="maxAnisotropy of every sampler, 1..16 (default: off, the isotropic sampler)")
-    ap.add_argument("--environment", default=None, choices=["sky"], help="image-based lighting from a procedural environment (default: off, punctual lights only)")
+    ap.add_argument("--environment", default=None, metavar="sky|FILE.hdr", help="image-based lighting from the procedural environment `sky` or from a Radiance .hdr panorama, built on the GPU (default: off, punctual lights only)")
+    ap.add_argument("--skybox", action="store_true", help="show the environment behind the model (pixels without geometry)")
     ap.add_argument("--view", default=None, metavar="NAME", help="write this debug view (e.g. meshlets) instead of the tone-mapped frame")
     a = ap.parse_args()
     from basicrenderer_amd import Scene
@@ -54,7 +55,10 @@ def main():
         r.set_anisotropy(a.anisotropy)
     if a.environment == "sky":
         from basicrenderer_amd.environment import Environment
-        r.set_environment(Environment.procedural(64))
+        r.set_environment(Environment.procedural(64), skybox=a.skybox)
+    elif a.environment:
+        from basicrenderer_amd.environment import Environment, read_hdr
+        r.set_environment(Environment.from_equirect(read_hdr(a.environment)), skybox=a.skybox)
     if a.view:
         r.set_debug_view(a.view)
     r.execute(); r.execute()

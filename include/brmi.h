@@ -294,14 +294,56 @@ int brmi_set_sampler_anisotropy(brmi_pass* pass, const uint32_t* maxAnisotropy, 
  * brmi_update) an activeEnvironmentIndex >= environmentCount.  What the host cannot see is the caller's contract: the six faces of a cubemap are square, of one
  * size, mipCount and BRMI_TEXTURE_FORMAT_RGBA8_UNORM, every chain inside its allocation.  The kernel reads each face by that face's own descriptor, clamps texel
  * coordinates and levels to it, and reads a cubemap index >= cubemapCount or a descriptor without texels, size or levels (or with more than
- * BRMI_TEXTURE_MAX_MIPS) as zero radiance: it never faults on a table that disagrees with itself. */
+ * BRMI_TEXTURE_MAX_MIPS) as zero radiance: it never faults on a table that disagrees with itself.
+ * The PREFILTERED cube stays RGBA8 (the reference's R8G8B8A8_UNorm; brmi_env_prefilter writes that): the shading pass takes every face of it as
+ * BRMI_TEXTURE_FORMAT_RGBA8_UNORM.  Only the cube cubeMapDescriptorIndex names -- the one the skybox stage shows -- may be BRMI_TEXTURE_FORMAT_RGBA16_FLOAT.
+ * `skybox` (the reference's SkyboxRenderPass, Deferred -> Skybox -> Forward): with it set, brmi_execute / brmi_execute_split run brmi_skybox behind the shading
+ * stage on the shading stream, in front of the debug-view stage; without it a frame launches exactly what it launched before the field existed.  structSize
+ * says whether the field is there: a struct of the size before it (BRMI_ENVIRONMENT_BUFFERS_SIZE_V1) is accepted and means `skybox` = 0. */
 typedef struct brmi_environment_buffers {
     uint32_t structSize;
     uint32_t specularIBL;                        /* PSO_SPECULAR_IBL: the reference defines it whenever screen-space reflections are off (PSOManager.cpp:1908-1913) */
     const brmi_environment_info* environments;   uint32_t environmentCount;   /* Builtin::Environment::InfoBuffer, device */
+    uint32_t reserved0;                          /* (the padding of the first layout: not read) */
     const brmi_texture_desc*     cubemaps;       uint32_t cubemapCount;       /* device; cubemap c = entries 6c .. 6c+5 in the order +X -X +Y -Y +Z -Z */
-} brmi_environment_buffers;
+    uint32_t reserved1;                          /* (the padding of the first layout: not read) */
+    uint32_t skybox;                             /* 0 / 1; read only when structSize covers it */
+    uint32_t reserved2[3];                       /* room for the next switches, zero for now.  (They also keep sizeof - 8 from being the first layout's size,
+                                                    which stays an accepted structSize: a struct that has lost its last fields must not pass for the old one.) */
+} brmi_environment_buffers;                      /* 56 B */
+#define BRMI_ENVIRONMENT_BUFFERS_SIZE_V1 40u     /* the struct up to and including cubemapCount's padding */
 int brmi_set_environment(brmi_pass* pass, const brmi_environment_buffers* env);
+/* SkyboxRenderPass (BR/shaders/skybox.hlsl): every pixel of the band whose linear depth is "empty" (0x7F7FFFFF) gets the lod-0 lookup of cubemap
+ * cubeMapDescriptorIndex of the frame's environment (RGBA16F or RGBA8) along its view ray as half4(colour, 1) in the lit HDR target, and currentNdc - prevNdc of
+ * that direction in the motion-vector plane (rg16f); pixels with geometry are not touched.  One wave per 8x8 tile of the surfaces' layout; a tile without an
+ * empty pixel ends before it loads the camera.  IEEE fp32 without contraction, normalize = v * (1 / sqrt(dot(v, v))) with both correctly rounded.
+ * Row bands write their rows only; the interleaved partition works as in the shading pass (the row table of the compact surfaces names the frame's rows).
+ * BRMI_ERR_STATE before brmi_setup / brmi_update, or without a bound environment whose `skybox` is set. */
+int brmi_skybox(brmi_pass* pass, brmi_stream stream);
+
+/* ---- environment build: the reference's EnvironmentConversionPass, EnvironmentSHPass and EnvironmentFilterPass ---------------------------
+ * Three stages on caller-owned DEVICE memory; they need no pass.  Every descriptor table is a device pointer; a cube is six brmi_texture_desc in the order
+ * +X -X +Y -Y +Z -Z.  Each kernel reads and writes every face through that face's own descriptor, clamps to it, and skips a face whose descriptor has no texels,
+ * size or levels, or not the format the stage writes: it never faults on a table that disagrees with itself (chains inside their allocations are the caller's
+ * contract, as for brmi_set_environment).  Lookups of the source are SampleLevel(g_linearClamp, .., 0) by the definition of DESIGN.md 2 (the reference's source cube
+ * has one level), RGBA16F or RGBA8.
+ * Refused with BRMI_ERR_INVALID before any launch: a null table, size == 0 or > 16384, levels == 0 or > BRMI_TEXTURE_MAX_MIPS, a destination format other than the
+ * one the stage writes (convert: RGBA16_FLOAT, prefilter: RGBA8_UNORM), environmentIndex >= environmentCount.
+ *
+ * brmi_env_convert     envToCubemap.hlsl: the equirectangular `equirect` (one descriptor, level 0) to the six faces of `cube`, size x size, alpha 1.
+ * brmi_env_project_sh  sphericalHarmonics.hlsl: the 27 integers of environments[environmentIndex] from cubemap cubeMapDescriptorIndex of that record (size = its
+ *                      face size, the reference's root constant); the 27 words are zeroed first and sphericalHarmonicsScale = 4 pi / (size^2 * 6) is written.
+ *                      Integer sums, added as unsigned: the result does not depend on the order and wraps where the reference's InterlockedAdd wraps.
+ * brmi_env_prefilter   blurEnvironment.hlsl + EnvironmentFilterPass.h:99-127: level m of `prefiltered` (size_m = max(1, size >> m)) with roughness m / (levels - 1)
+ *                      (0 for one level), 16 GGX samples, RGBA8 UNORM (saturate, round to nearest), alpha 255.
+ * brmi_env_build_bytes bytes of the RGBA16F cube (*cubeBytes) and of the RGBA8 chain of `levels` levels (*prefilteredBytes), six faces each, tightly packed;
+ *                      returns their sum (0 for a refused size / levels).  Either pointer may be null. */
+int brmi_env_convert(const brmi_texture_desc* equirect, const brmi_texture_desc* cube, uint32_t size, uint32_t cubeFormat, brmi_stream stream);
+int brmi_env_project_sh(const brmi_texture_desc* cubemaps, uint32_t cubemapCount, brmi_environment_info* environments, uint32_t environmentCount,
+                        uint32_t environmentIndex, uint32_t size, brmi_stream stream);
+int brmi_env_prefilter(const brmi_texture_desc* sourceCube, const brmi_texture_desc* prefiltered, uint32_t size, uint32_t levels, uint32_t prefilteredFormat,
+                       brmi_stream stream);
+uint64_t brmi_env_build_bytes(uint32_t size, uint32_t levels, uint64_t* cubeBytes, uint64_t* prefilteredBytes);
 
 /* Debug views.  brmi_set_debug_view binds the targets (NULL unbinds and gives exactly the frames of a pass that never called it); with a target bound and
  * perFrame.outputType != 0, brmi_execute / brmi_execute_split run brmi_debug_view behind the shading stage (on the shading stream); an outputType the stage
@@ -427,6 +469,10 @@ int brmi_debug_ibl_lookup(const brmi_environment_buffers* env, uint32_t cubemapI
 int brmi_debug_ibl(brmi_pass* pass, const brmi_environment_buffers* env, uint32_t environmentIndex, const float* normals, const uint32_t* albedo,
                    const uint32_t* metallicRoughness, const uint64_t* coat, const uint64_t* emissive, const uint64_t* fuzz, const float* viewWS,
                    float* outDiffuse, float* outSpecular, uint32_t n, brmi_stream stream);
+/* The cube lookup of the environment build and the skybox stage, which honours the format of the face descriptor it lands on (RGBA16_FLOAT: halves decoded exactly;
+ * anything else: the RGBA8 path of brmi_debug_ibl_lookup).  Arguments as brmi_debug_ibl_lookup's, the table given directly; those stages call it with lod 0. */
+int brmi_debug_env_lookup(const brmi_texture_desc* cubemaps, uint32_t cubemapCount, uint32_t cubemapIndex, const float* directions, const float* lods,
+                          float* outRGBA, uint32_t n, brmi_stream stream);
 
 #ifdef __cplusplus
 }

@@ -404,6 +404,9 @@ typedef struct brmi_openpbr_material_info {
  * bound with brmi_set_sampler_anisotropy; without the table every sampler filters isotropically. */
 #define BRMI_TEXTURE_FORMAT_RGBA8_UNORM       0u
 #define BRMI_TEXTURE_FORMAT_RGBA8_UNORM_SRGB  1u     /* rgb decoded through brmi_scene_buffers::srgbToLinear before filtering */
+/* Four IEEE halves per texel (8 B; `texels` 8-byte aligned; mipOffset stays in TEXELS): the reference's environment cube, R16G16B16A16_Float.  Only the environment
+ * build (brmi_env_*) and the skybox stage (brmi_skybox) honour it; the material sampler, the alpha test and the shading pass's prefiltered cube read RGBA8. */
+#define BRMI_TEXTURE_FORMAT_RGBA16_FLOAT      2u
 #define BRMI_TEXTURE_MAX_MIPS                 16u
 typedef struct brmi_texture_desc {
     const uint8_t* texels;                  /* device pointer, 4-byte aligned (scene generator output: byte offset into BRMI_ARR_TEXELS) */
@@ -426,7 +429,8 @@ typedef struct brmi_sampler_desc {
  * EnvironmentInfo, BR/include/ShaderBuffers.h:453-459 / BR/shaders/Include/structs.hlsli:627-633, byte for byte.  The 27 integers are nine RGB
  * coefficients of irradianceSH (BR/shaders/Include/IBL.hlsli:8-23: basis 1, y, z, x, yx, yz, 3z^2 - 1, zx, x^2 - y^2), each worth
  * value * sphericalHarmonicsScale / BRMI_SH_FLOAT_SCALE.  prefilteredCubemapDescriptorIndex counts whole cubemaps of
- * brmi_environment_buffers::cubemaps (brmi.h); cubeMapDescriptorIndex (the skybox) is not read. */
+ * brmi_environment_buffers::cubemaps (brmi.h), and so does cubeMapDescriptorIndex: the cube the skybox stage shows (brmi_skybox) and the SH projection
+ * reads (brmi_env_project_sh); the shading pass does not read it. */
 #define BRMI_SH_FLOAT_SCALE 100                 /* BR/shaders/Include/constants.hlsli:6-7 */
 #define BRMI_IBL_PREFILTER_LEVELS 12u           /* prefilteredRadiance, IBL.hlsli:85-92: lod = roughness * (12 - 1) */
 typedef struct brmi_environment_info {
