@@ -41,9 +41,9 @@ __global__ void k_debug_arith_in_range(const float* a, float* outRcp, float* out
 }
 
 int fail(brmi_pass* p, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
-    if (p) p->err = buf;
+    std::string msg;
+    va_list ap; va_start(ap, fmt); vrefuse(msg, code, fmt, ap); va_end(ap);
+    if (p) p->err = msg;
     return code;
 }
 
@@ -104,12 +104,12 @@ static void compute_sizes(brmi_pass* p) {
     w.wordPrefix = take((uint64_t)p->totalWords * 4);
     w.blockSums = take((uint64_t)(p->scanBlocks + 1) * 4);
     w.scanAgg = take(65 * 8);
-    w.instanceBitBase = take((uint64_t)std::max<size_t>(1, p->hostInstanceBitBase.size()) * 4);
-    w.segPrefix = take((uint64_t)std::max<size_t>(1, p->hostSegPrefix.size()) * 4);
-    w.meshLevelWidth = take((uint64_t)std::max<size_t>(1, p->hostMeshLevelWidth.size()) * 4);
-    w.flatNodes = take((uint64_t)std::max<size_t>(1, p->hostFlatNodes.size()) * sizeof(FlatNode));
-    w.flatLeaves = take((uint64_t)std::max<size_t>(1, p->hostFlatLeaves.size()) * sizeof(FlatLeaf));
-    w.instanceWalk = take((uint64_t)std::max<size_t>(1, p->hostInstanceWalk.size()) * sizeof(InstanceWalk));
+    w.instanceBitBase = take((uint64_t)std::max<size_t>(1, p->tables.instanceBitBase.size()) * 4);
+    w.segPrefix = take((uint64_t)std::max<size_t>(1, p->tables.segPrefix.size()) * 4);
+    w.meshLevelWidth = take((uint64_t)std::max<size_t>(1, p->tables.meshLevelWidth.size()) * 4);
+    w.flatNodes = take((uint64_t)std::max<size_t>(1, p->tables.flatNodes.size()) * sizeof(FlatNode));
+    w.flatLeaves = take((uint64_t)std::max<size_t>(1, p->tables.flatLeaves.size()) * sizeof(FlatLeaf));
+    w.instanceWalk = take((uint64_t)std::max<size_t>(1, p->tables.instanceWalk.size()) * sizeof(InstanceWalk));
     w.planes = take((uint64_t)2 * c.lightClusterSize[2] * 4);
     // phase-1 -> phase-2 hand-over (reference: clodStructs.hlsli:629-652); the replay bucket array doubles as the
     // phase-2 bucket array, so it has the full record capacity
@@ -160,17 +160,17 @@ static void compute_sizes(brmi_pass* p) {
     w.listRecords = take((uint64_t)p->lightPagePool * BRMI_LIGHTS_PER_PAGE * 64 + 4096);      // ... and the lights' 64 B shading records in the same order        // the page contents once more, in the order the page walk visits them
     // textured / alpha-tested scenes only: where each visible cluster's UV set lives, the texcoords of the resolve arena's vertices,
     // and the alpha-test operands that travel with binned triangles
-    const bool uvs = p->sceneHasTextures || p->sceneHasAlphaTest || p->sceneHasVertexColors;
+    const bool uvs = p->tables.hasTextures || p->tables.hasAlphaTest || p->tables.hasVertexColors;
     w.clusterUv = take(uvs ? (uint64_t)c.maxVisibleClusters * 32 : 16);
-    w.resolveColors = take(p->sceneHasVertexColors ? (uint64_t)p->resolveCapacity * 4 : 16);
-    w.resolveUVs = take(p->sceneHasTextures ? (uint64_t)p->resolveCapacity * 8 * p->sceneUvSets : 16);
-    w.binAlpha = take(p->sceneHasAlphaTest ? (uint64_t)p->binsX * p->binsY * p->binCapacity * 48 : 16);
-    w.overflowAlpha = take(p->sceneHasAlphaTest ? (uint64_t)CNT_STRIPE_COUNT * p->binOverflowPerStripe * 48 : 16);
-    w.alphaMats = take(p->sceneHasAlphaTest ? (uint64_t)std::max(1u, p->scene.materialCount) * 128 : 16);
+    w.resolveColors = take(p->tables.hasVertexColors ? (uint64_t)p->resolveCapacity * 4 : 16);
+    w.resolveUVs = take(p->tables.hasTextures ? (uint64_t)p->resolveCapacity * 8 * p->tables.uvSets : 16);
+    w.binAlpha = take(p->tables.hasAlphaTest ? (uint64_t)p->binsX * p->binsY * p->binCapacity * 48 : 16);
+    w.overflowAlpha = take(p->tables.hasAlphaTest ? (uint64_t)CNT_STRIPE_COUNT * p->binOverflowPerStripe * 48 : 16);
+    w.alphaMats = take(p->tables.hasAlphaTest ? (uint64_t)std::max(1u, p->scene.materialCount) * 128 : 16);
     // round 6, the draw list: per-meshlet boxes of the resident pages, the (slab, page) -> first box table, and the three lists of a frame
-    w.meshletBoxes = take((uint64_t)std::max(1u, p->totalBoxes) * sizeof(MeshletBox));
-    w.pageBoxBase = take((uint64_t)std::max<size_t>(1, p->hostPageBoxBase.size()) * 4);
-    w.pageRefs = take((uint64_t)std::max<size_t>(1, p->hostPageRefs.size()) * sizeof(PageRef));
+    w.meshletBoxes = take((uint64_t)std::max(1u, p->tables.totalBoxes) * sizeof(MeshletBox));
+    w.pageBoxBase = take((uint64_t)std::max<size_t>(1, p->tables.pageBoxBase.size()) * 4);
+    w.pageRefs = take((uint64_t)std::max<size_t>(1, p->tables.pageRefs.size()) * sizeof(PageRef));
     w.drawList = take(p->holdEnabled ? (uint64_t)c.maxVisibleClusters * 4 : 16);
     w.generalList = take(p->leanMinClusters != 0u ? (uint64_t)c.maxVisibleClusters * 4 : 16);
     w.bigQueue = take(p->leanMinClusters != 0u ? (uint64_t)p->leanQueue * 96 : 16);      // WideTri
@@ -178,7 +178,7 @@ static void compute_sizes(brmi_pass* p) {
     w.heldRecords = take(p->holdEnabled ? (uint64_t)c.maxVisibleClusters * sizeof(HeldRecord) : 16);
     w.lateList = take(p->holdEnabled ? (uint64_t)c.maxVisibleClusters * 4 : 16);
     w.wideQueue = take((uint64_t)std::max(1u, p->wideCapacity) * 96);      // WideTri (brmi_raster.hip)
-    w.wideAlpha = take(p->sceneHasAlphaTest ? (uint64_t)std::max(1u, p->wideCapacity) * 48 : 16);
+    w.wideAlpha = take(p->tables.hasAlphaTest ? (uint64_t)std::max(1u, p->wideCapacity) * 48 : 16);
     w.total = off;
     p->resNeed[BRMI_RES_WORKSPACE] = w.total;
 }
@@ -306,8 +306,8 @@ void brmi_destroy(brmi_pass* p) {
 
 const char* brmi_last_error(const brmi_pass* p) { return p ? p->err.c_str() : "null pass"; }
 
-// Provider resolution.  Also derives the static rank tables of the deterministic visible-cluster
-// compaction (per-instance bit base, per-segment meshlet prefix) and the BVH level bound.
+// Provider resolution.  Copies the scene's arrays to the host once and hands them to analyse_scene (brmi_scene_tables.h), which
+// validates the cross references and derives brmi_pass::tables; what follows sizes the workspace from them.
 int brmi_set_scene(brmi_pass* p, const brmi_scene_buffers* scene) {
     if (!p || !scene) return BRMI_ERR_INVALID;
     p->scene = *scene; p->haveScene = false; p->setupDone = false;
@@ -320,250 +320,38 @@ int brmi_set_scene(brmi_pass* p, const brmi_scene_buffers* scene) {
         return fail(p, BRMI_ERR_INVALID, "brmi_set_scene: a required scene buffer is null");
     if (!sc.lutOpaqueDielectricEnergyComplement || !sc.lutOpaqueDielectricAvgEnergyComplement || !sc.lutIdealMetalEnergyComplement || !sc.lutIdealMetalAvgEnergyComplement || !sc.lutFuzzLTC)
         return fail(p, BRMI_ERR_INVALID, "brmi_set_scene: OpenPBR lookup tables must be provided");
-    std::vector<brmi_clod_mesh_metadata> md; std::vector<brmi_mesh_instance_clod_offsets> offs; std::vector<brmi_lod_node> nodes; std::vector<brmi_lod_segment> segs;
-    int rc;
-    if ((rc = read_back(p, md, sc.meshMetadata, sc.meshMetadataCount))) return rc;
-    if ((rc = read_back(p, offs, sc.clodOffsets, sc.perMeshInstanceCount))) return rc;
-    if ((rc = read_back(p, nodes, sc.lodNodes, sc.lodNodeCount))) return rc;
-    if ((rc = read_back(p, segs, sc.lodSegments, sc.lodSegmentCount))) return rc;
-    {   // which layered shading variants the scene can need (materials edited on the device later: call brmi_set_scene again)
-        std::vector<brmi_openpbr_material_info> op;
-        if ((rc = read_back(p, op, sc.openpbrMaterials, sc.openpbrMaterialCount))) return rc;
-        p->sceneHasCoat = p->sceneHasFuzz = false;
-        bool layerTextures = false;
-        // UV sets the G-buffer pass must decode: 1 + the highest set an enabled texture slot names (AppendClodMaterialUvSample: an index >= 8 reads set 0)
-        uint32_t uvSets = 1;
-        auto names_set = [&](uint32_t setIndex) { if (setIndex < 8u && setIndex + 1u > uvSets) uvSets = setIndex + 1u; };
-        for (size_t i = 0; i < op.size(); i++) {
-            const auto& m = op[i];
-            if (m.coatWeight > 0.0f) p->sceneHasCoat = true;
-            if (m.fuzzWeight > 0.0f) p->sceneHasFuzz = true;
-            // HasOpenPBRTexture (utilities.hlsli:643-646): a coat / fuzz slot with a valid texture AND sampler index is sampled
-            for (int k = 0; k < 6; k++)
-                if (m.textureBindings[2 * k] != 0xFFFFFFFFu && m.textureBindings[2 * k + 1] != 0xFFFFFFFFu) {
-                    layerTextures = true;
-                    names_set(m.textureBindings[26 + k]);
-                }
-        }
-        // texture slots: the alpha-test variants of the rasteriser and the texture-sampling variant of the G-buffer pass are only
-        // launched for scenes that need them
-        if (sc.openpbrMaterialCount > 65536u) return fail(p, BRMI_ERR_CAPACITY, "brmi_set_scene: %u OpenPBR material records; the shading pass folds 66 KB of table rows per record and takes at most 65536", sc.openpbrMaterialCount);
-        std::vector<brmi_material_info> mats;
-        if ((rc = read_back(p, mats, sc.materials, sc.materialCount))) return rc;
-        p->sceneHasAlphaTest = false; p->sceneHasTextures = layerTextures; p->sceneHasParallax = false;
-        for (size_t i = 0; i < mats.size(); i++) {
-            const brmi_material_info& m = mats[i];
-            if (m.materialFlags & BRMI_MATERIAL_PARALLAX) names_set(m.heightUvSetIndex);
-            if (m.materialFlags & BRMI_MATERIAL_ALPHA_TEST) p->sceneHasAlphaTest = true;
-            if (m.materialFlags & BRMI_MATERIAL_PARALLAX) p->sceneHasParallax = true;
-            if (m.materialFlags & BRMI_MATERIAL_ANY_TEXTURE) {
-                p->sceneHasTextures = true;
-                const uint32_t f = m.materialFlags;
-                if (f & BRMI_MATERIAL_BASE_COLOR_TEXTURE) names_set(m.baseColorUvSetIndex);
-                if (f & BRMI_MATERIAL_NORMAL_MAP) names_set(m.normalUvSetIndex);
-                if (f & BRMI_MATERIAL_METALLIC_TEXTURE) names_set(m.metallicUvSetIndex);
-                if (f & BRMI_MATERIAL_ROUGHNESS_TEXTURE) names_set(m.roughnessUvSetIndex);
-                if (f & BRMI_MATERIAL_EMISSIVE_TEXTURE) names_set(m.emissiveUvSetIndex);
-                if (f & BRMI_MATERIAL_AO_TEXTURE) names_set(m.aoUvSetIndex);
-                // the opacity slot only feeds the alpha channel, which the G-buffer does not store; the rasteriser's alpha test reads UV set 0 as the reference's does
-            }
-        }
-        p->sceneUvSets = uvSets;
-        std::vector<brmi_per_mesh> pms;
-        if ((rc = read_back(p, pms, sc.perMesh, sc.perMeshCount))) return rc;
-        p->sceneHasVertexColors = false;
-        for (const auto& pm : pms) if (pm.vertexFlags & 1u) p->sceneHasVertexColors = true;       // VERTEX_COLORS (BR/include/Mesh/VertexFlags.h)
-        if (p->sceneHasTextures && (!sc.textures || !sc.samplers || !sc.srgbToLinear || sc.textureCount == 0 || sc.samplerCount == 0))
-            return fail(p, BRMI_ERR_INVALID, "brmi_set_scene: materials sample textures but the texture / sampler tables or the sRGB decode table are missing");
-    }
-    {   // Cross references the kernels follow unchecked: validated once here, on the host copies (a bad index is an error message, not a
-        // GPU fault).  Page contents (headers, descriptors, streams inside the slabs) are NOT walked: they are the builder's contract.
-        std::vector<brmi_per_mesh_instance> insts; std::vector<uint32_t> draws; std::vector<brmi_per_mesh> pms; std::vector<brmi_material_info> mats;
-        std::vector<brmi_group_page_map_entry> pmap; std::vector<brmi_lod_group> groups; std::vector<brmi_per_object> objs;
-        if ((rc = read_back(p, insts, sc.perMeshInstance, sc.perMeshInstanceCount))) return rc;
-        if ((rc = read_back(p, draws, sc.activeDraws, sc.activeDrawCount))) return rc;
-        if ((rc = read_back(p, pms, sc.perMesh, sc.perMeshCount))) return rc;
-        if ((rc = read_back(p, mats, sc.materials, sc.materialCount))) return rc;
-        if ((rc = read_back(p, pmap, sc.groupPageMap, sc.groupPageMapCount))) return rc;
-        if ((rc = read_back(p, groups, sc.lodGroups, sc.lodGroupCount))) return rc;
-        if ((rc = read_back(p, objs, sc.perObject, sc.perObjectCount))) return rc;
-        for (size_t i = 0; i < draws.size(); i++) if (draws[i] >= insts.size()) return fail(p, BRMI_ERR_INVALID, "activeDraws[%zu] = %u: no such mesh instance", i, draws[i]);
-        for (size_t i = 0; i < insts.size(); i++) {
-            if (insts[i].perMeshBufferIndex >= pms.size()) return fail(p, BRMI_ERR_INVALID, "mesh instance %zu: perMeshBufferIndex %u out of range", i, insts[i].perMeshBufferIndex);
-            if (insts[i].perObjectBufferIndex >= sc.perObjectCount) return fail(p, BRMI_ERR_INVALID, "mesh instance %zu: perObjectBufferIndex %u out of range", i, insts[i].perObjectBufferIndex);
-            if ((pms[insts[i].perMeshBufferIndex].vertexFlags & BRMI_VERTEX_SKINNED) && insts[i].skinningInstanceSlot != 0xFFFFFFFFu &&
-                ((uint64_t)insts[i].skinningInstanceSlot + 1u) * 64u > sc.skinningMatrixCount)
-                return fail(p, BRMI_ERR_INVALID, "mesh instance %zu: skinning slot %u lies outside the skinning matrix buffer", i, insts[i].skinningInstanceSlot);
-        }
-        for (size_t i = 0; i < pms.size(); i++) if (pms[i].materialDataIndex >= mats.size()) return fail(p, BRMI_ERR_INVALID, "mesh %zu: materialDataIndex %u out of range", i, pms[i].materialDataIndex);
-        for (size_t i = 0; i < mats.size(); i++) if (mats[i].openPBRMaterialDataIndex >= sc.openpbrMaterialCount) return fail(p, BRMI_ERR_INVALID, "material %zu: openPBRMaterialDataIndex %u out of range", i, mats[i].openPBRMaterialDataIndex);
-        for (size_t i = 0; i < pmap.size(); i++) {
-            if (pmap[i].slabDescriptorIndex >= sc.slabCount) return fail(p, BRMI_ERR_INVALID, "page map entry %zu: slab %u out of range", i, pmap[i].slabDescriptorIndex);
-            if (pmap[i].slabByteOffset % BRMI_PAGE_SIZE) return fail(p, BRMI_ERR_INVALID, "page map entry %zu: offset %u is not a page boundary", i, pmap[i].slabByteOffset);
-        }
-        for (size_t m = 0; m < md.size(); m++) if (md[m].groupsBase > groups.size() || md[m].segmentsBase > segs.size() || md[m].pageMapBase > pmap.size()) return fail(p, BRMI_ERR_INVALID, "mesh metadata %zu: base index out of range", m);
-        for (size_t i = 0; i < offs.size(); i++) if (offs[i].clodMeshMetadataIndex >= md.size()) return fail(p, BRMI_ERR_INVALID, "instance %zu: bad mesh metadata index", i);
-        // segments -> pages and refined groups, relative to the mesh that owns them (a mesh's segments end where the next mesh's begin)
-        std::vector<uint32_t> order(md.size());
-        for (size_t m = 0; m < md.size(); m++) order[m] = (uint32_t)m;
-        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return md[a].segmentsBase < md[b].segmentsBase; });
-        for (size_t k = 0; k < order.size(); k++) {
-            const brmi_clod_mesh_metadata& mm = md[order[k]];
-            const size_t segEnd = k + 1 < order.size() ? md[order[k + 1]].segmentsBase : segs.size();
-            for (size_t si = mm.segmentsBase; si < segEnd; si++) {
-                if ((uint64_t)mm.pageMapBase + segs[si].pageIndex >= pmap.size()) return fail(p, BRMI_ERR_INVALID, "segment %zu: page %u lies outside the group page map", si, segs[si].pageIndex);
-                if (segs[si].refinedGroup >= 0 && (uint64_t)mm.groupsBase + (uint32_t)segs[si].refinedGroup >= groups.size()) return fail(p, BRMI_ERR_INVALID, "segment %zu: refined group %d out of range", si, segs[si].refinedGroup);
-            }
-        }
-    }
-    // per mesh: walk the BVH, collect the segments its leaves reference, depth of the tree
-    p->hostSegPrefix.assign(segs.size(), 0);
-    std::vector<uint32_t> meshBits(md.size(), 0);
-    uint32_t maxDepth = 1;
-    p->maxLevelWidth = 1; p->minLevelWidth = 0xFFFFFFFFu; p->hostMeshLevelWidth.assign(md.size(), 1u);
-    p->spillLevels = 0;
-    std::vector<uint32_t> levelWidth;
-    std::vector<std::pair<uint32_t, uint32_t>> stack;
-    for (size_t m = 0; m < md.size(); m++) {
-        uint32_t segCount = 0;
-        levelWidth.assign(66, 0);
-        stack.clear(); stack.push_back({md[m].rootNode, 1});
-        while (!stack.empty()) {
-            auto [n, d] = stack.back(); stack.pop_back();
-            if ((uint64_t)md[m].lodNodesBase + n >= nodes.size()) return fail(p, BRMI_ERR_INVALID, "mesh %zu: node %u out of range", m, n);
-            const brmi_lod_node& nd = nodes[md[m].lodNodesBase + n];
-            maxDepth = std::max(maxDepth, d);
-            if (d < levelWidth.size()) p->hostMeshLevelWidth[m] = std::max(p->hostMeshLevelWidth[m], ++levelWidth[d]);
-            if (nd.isLeaf != BRMI_NODE_INTERNAL) {
-                // a leaf names its group and (countMinusOne - 1) the group that refines it: the traversal reads both records unchecked
-                if ((uint64_t)md[m].groupsBase + nd.ownerGroupId >= sc.lodGroupCount) return fail(p, BRMI_ERR_INVALID, "mesh %zu: leaf node %u names group %u, which does not exist", m, n, nd.ownerGroupId);
-                if (nd.countMinusOne != 0u && (uint64_t)md[m].groupsBase + (nd.countMinusOne - 1u) >= sc.lodGroupCount) return fail(p, BRMI_ERR_INVALID, "mesh %zu: leaf node %u names refined group %u, which does not exist", m, n, nd.countMinusOne - 1u);
-                segCount = std::max(segCount, nd.indexOrOffset + 1); continue;
-            }
-            if (d > 64) return fail(p, BRMI_ERR_INVALID, "mesh %zu: BVH deeper than 64 levels", m);
-            const uint32_t cc = std::min(nd.countMinusOne + 1u, BRMI_BVH_MAX_CHILDREN);
-            for (uint32_t k = 0; k < cc; k++) stack.push_back({nd.indexOrOffset + k, d + 1});
-        }
-        uint64_t run = 0;
-        for (uint32_t s = 0; s < segCount; s++) {
-            const size_t gi = (size_t)md[m].segmentsBase + s;
-            if (gi >= segs.size()) return fail(p, BRMI_ERR_INVALID, "mesh %zu: segment %u out of range", m, s);
-            p->hostSegPrefix[gi] = (uint32_t)run; run += segs[gi].meshletCount;
-        }
-        if (run > 0xFFFFFFFFull) return fail(p, BRMI_ERR_CAPACITY, "mesh %zu has too many meshlets", m);
-        meshBits[m] = (uint32_t)run;
-        p->maxLevelWidth = std::max(p->maxLevelWidth, p->hostMeshLevelWidth[m]); p->minLevelWidth = std::min(p->minLevelWidth, p->hostMeshLevelWidth[m]);
-        if (p->hostMeshLevelWidth[m] > p->spillWidth) {
-            // a mesh too wide for the LDS walk: the walk hands its frontier to the level kernels at the first level that holds more than 128 nodes
-            // (brmi_cull.hip, spill mode) -- never above the first level that CAN hold that many; what is left below bounds the level launches
-            uint32_t depth = 1, first = 0;
-            for (uint32_t d = 1; d < levelWidth.size(); d++) { if (levelWidth[d]) depth = d; if (!first && levelWidth[d] > 128u) first = d; }
-            if (first) p->spillLevels = std::max(p->spillLevels, depth - first + 1u);
-        }
-    }
-    p->hostInstanceBitBase.assign(offs.size(), 0);
-    uint64_t bits = 0;
-    for (size_t i = 0; i < offs.size(); i++) {
-        if (offs[i].clodMeshMetadataIndex >= md.size()) return fail(p, BRMI_ERR_INVALID, "instance %zu: bad mesh metadata index", i);
-        p->hostInstanceBitBase[i] = (uint32_t)bits; bits += meshBits[offs[i].clodMeshMetadataIndex];
-        if (bits > 0xFFFFFFF0ull) return fail(p, BRMI_ERR_CAPACITY, "scene exceeds 2^32 (instance, meshlet) pairs");
-    }
-    {   // flat traversal tables: the BVH of a mesh with at most 8192 nodes, breadth-first, with what its leaves' groups and segments say folded in
-        std::vector<brmi_lod_group> groups; std::vector<brmi_per_mesh_instance> insts; std::vector<brmi_per_mesh> pms;
-        int rc2;
-        if ((rc2 = read_back(p, groups, sc.lodGroups, sc.lodGroupCount))) return rc2;
-        if ((rc2 = read_back(p, insts, sc.perMeshInstance, sc.perMeshInstanceCount))) return rc2;
-        if ((rc2 = read_back(p, pms, sc.perMesh, sc.perMeshCount))) return rc2;
-        p->hostFlatNodes.clear(); p->hostFlatLeaves.clear(); p->flatMaxDepth = 1;
-        std::vector<uint32_t> flatBase(md.size(), 0), flatCount(md.size(), 0);
-        const bool flatOn = tuning("flat_traversal", 1) != 0;
-        std::vector<std::pair<uint32_t, uint32_t>> bfs;      // (node id, parent position)
-        for (size_t m = 0; flatOn && m < md.size(); m++) {
-            bfs.clear(); bfs.push_back({md[m].rootNode, 0u});
-            bool fits = true;
-            for (size_t k = 0; k < bfs.size() && fits; k++) {
-                const brmi_lod_node& nd = nodes[md[m].lodNodesBase + bfs[k].first];
-                if (nd.isLeaf != BRMI_NODE_INTERNAL) continue;
-                const uint32_t cc = std::min(nd.countMinusOne + 1u, BRMI_BVH_MAX_CHILDREN);
-                for (uint32_t c = 0; c < cc; c++) { bfs.push_back({nd.indexOrOffset + c, (uint32_t)k}); if (bfs.size() > 8192) { fits = false; break; } }
-            }
-            if (!fits) continue;
-            flatBase[m] = (uint32_t)p->hostFlatNodes.size(); flatCount[m] = (uint32_t)bfs.size();
-            // (breadth-first: the children of a node are pushed together, so they sit side by side; position of the first and depth of every node)
-            std::vector<uint32_t> firstChild(bfs.size(), 0u), childCount(bfs.size(), 0u), depthOf(bfs.size(), 1u);
-            uint32_t meshDepth = 1u;
-            for (size_t k = 1; k < bfs.size(); k++) { const uint32_t par = bfs[k].second; if (childCount[par]++ == 0u) firstChild[par] = (uint32_t)k; depthOf[k] = depthOf[par] + 1u; meshDepth = std::max(meshDepth, depthOf[k]); }
-            // the level-synchronous traversal keeps a frontier size per level in counters[CNT_FRONTIER0 + level] (96 words up to the stripe statistics) and launches a kernel per
-            // level: a hierarchy deeper than that, or than the configured level bound, is left to the level walk
-            if (meshDepth > std::min<uint32_t>(std::max(1u, p->cfg.maxBvhLevels), CNT_STRIPES - CNT_FRONTIER0 - 1u)) { flatCount[m] = 0; continue; }
-            p->flatMaxDepth = std::max(p->flatMaxDepth, meshDepth);
-            for (size_t k = 0; k < bfs.size(); k++) {
-                const brmi_lod_node& nd = nodes[md[m].lodNodesBase + bfs[k].first];
-                FlatNode f{}; FlatLeaf l{};
-                f.children = firstChild[k] | (childCount[k] << 16);
-                std::memcpy(f.cull, nd.cullCenterAndRadius, 16); std::memcpy(f.lod, nd.lodCenterAndRadius, 16); f.maxQuadricError = nd.maxQuadricError;
-                f.nodeId = bfs[k].first; f.info = bfs[k].second << 8;
-                if (nd.isLeaf == BRMI_NODE_INTERNAL) f.info |= 1u;
-                else {
-                    const brmi_lod_group& g = groups[md[m].groupsBase + nd.ownerGroupId];
-                    std::memcpy(l.group, g.centerAndRadius, 16); l.ownerGlobal = md[m].groupsBase + nd.ownerGroupId;
-                    if (nd.countMinusOne != 0u) { const brmi_lod_group& cg = groups[md[m].groupsBase + (nd.countMinusOne - 1u)]; std::memcpy(l.child, cg.centerAndRadius, 16); l.childParentError = cg.maxParentError; l.childGlobal = md[m].groupsBase + (nd.countMinusOne - 1u); f.info |= 1u << 1; }
-                    const size_t si = (size_t)md[m].segmentsBase + nd.indexOrOffset;
-                    if (si >= segs.size()) return fail(p, BRMI_ERR_INVALID, "mesh %zu: leaf node %u names segment %u, which does not exist", m, bfs[k].first, nd.indexOrOffset);
-                    if (segs[si].meshletCount != 0u) f.info |= 1u << 2;
-                    if (segs[si].meshletCount > 0xFFFFu || segs[si].firstMeshletInPage > 0xFFFFu) { flatCount[m] = 0; break; }      // (the bucket record packs both in 16 bits; leave such a mesh to the level walk)
-                    f.ownerGroup = nd.ownerGroupId; f.segFirstCount = segs[si].firstMeshletInPage | (segs[si].meshletCount << 16);
-                    f.pageMapIndex = md[m].pageMapBase + segs[si].pageIndex; f.firstBitRel = p->hostSegPrefix[si];
-                }
-                p->hostFlatNodes.push_back(f); p->hostFlatLeaves.push_back(l);
-            }
-            if (flatCount[m] == 0) { p->hostFlatNodes.resize(flatBase[m]); p->hostFlatLeaves.resize(flatBase[m]); }
-        }
-        p->anyWideFlat = false; p->allMeshesFlat = flatOn;
-        for (size_t m = 0; m < md.size(); m++) { if (flatCount[m] > 256u) p->anyWideFlat = true; if (flatCount[m] == 0u) p->allMeshesFlat = false; }
-        p->hostInstanceWalk.assign(offs.size(), InstanceWalk{0, 0, 0, 0});
-        for (size_t i = 0; i < offs.size() && i < insts.size(); i++) {
-            const uint32_t m = offs[i].clodMeshMetadataIndex;
-            const bool skinned = insts[i].perMeshBufferIndex < pms.size() && (pms[insts[i].perMeshBufferIndex].vertexFlags & BRMI_VERTEX_SKINNED) != 0;
-            p->hostInstanceWalk[i] = InstanceWalk{flatBase[m], flatCount[m], p->hostInstanceBitBase[i], skinned ? 1u : 0u};
-        }
-    }
-    {   // Round 6, the draw list: every resident page of the page map, and where its meshlets' boxes start in the side table (k_meshlet_boxes fills it in brmi_setup).
-        // A page's meshlet count is the first word of its header (the builder's contract; one small read-back per page, not per frame).
-        std::vector<brmi_group_page_map_entry> pmap;
-        if ((rc = read_back(p, pmap, sc.groupPageMap, sc.groupPageMapCount))) return rc;
-        std::vector<const uint8_t*> slabPtrs;
-        if ((rc = read_back(p, slabPtrs, reinterpret_cast<const uint8_t* const*>(sc.slabs), sc.slabCount))) return rc;
-        p->hostPageRefs.clear(); p->totalBoxes = 0;
-        p->hostPageBoxBase.assign((size_t)std::max(1u, sc.slabCount) * 1024u, 0xFFFFFFFFu);
-        const bool boxesOn = tuning("hold_clusters", 1) != 0 && p->cfg.enableOcclusionCulling && sc.slabCount <= 4096u;
-        for (size_t i = 0; boxesOn && i < pmap.size(); i++) {
-            const uint32_t slab = pmap[i].slabDescriptorIndex, page = pmap[i].slabByteOffset / BRMI_PAGE_SIZE;
-            if (slab == 0u || page >= 1024u || !slabPtrs[slab]) continue;      // not resident (or beyond the 10 page bits of the packed cluster: such a page is never named)
-            uint32_t& base = p->hostPageBoxBase[(size_t)slab * 1024u + page];
-            if (base != 0xFFFFFFFFu) continue;                                  // several groups share a page
-            uint32_t meshlets = 0;
-            BRMI_HIP(p, hipMemcpy(&meshlets, slabPtrs[slab] + pmap[i].slabByteOffset, 4, hipMemcpyDeviceToHost));
-            meshlets = std::min(meshlets, (BRMI_PAGE_SIZE - 64u) / 64u);
-            if ((uint64_t)p->totalBoxes + meshlets > 0x7FFFFFFFull) break;
-            base = p->totalBoxes;
-            p->hostPageRefs.push_back(PageRef{slab, pmap[i].slabByteOffset, base, meshlets});
-            p->totalBoxes += meshlets;
-        }
-        // (the interleaved partition keeps the whole list: its compact surfaces hold this GPU's chunks only -- the re-test would have to map rows.  A contiguous band
-        // lives in frame rows: the tests clamp their rectangles to it, and the chain's texels beyond it read "empty")
-        p->holdEnabled = boxesOn && p->totalBoxes != 0u && p->stripes.count <= 1u;
-        p->holdMinClusters = (uint32_t)std::max(0l, tuning("hold_min_clusters", p->holdMinClusters));
-        p->lateDirectMax = (uint32_t)std::max(0l, tuning("late_direct_max", p->lateDirectMax));
-        p->holdStillMax = (uint32_t)std::max(0l, tuning("hold_still_max", p->holdStillMax));
-        p->holdFloor = (uint32_t)std::max(0l, tuning("hold_floor", p->holdFloor));
-        p->holdMaxTexels = (uint32_t)std::min(16l, std::max(1l, tuning("hold_max_texels", p->holdMaxTexels)));
-        p->retestMaxTexels = (uint32_t)std::min(16l, std::max(1l, tuning("retest_max_texels", p->retestMaxTexels)));
-    }
-    p->totalBits = bits;
-    p->totalWords = (uint32_t)std::max<uint64_t>(1, (bits + 31) / 32);
+    // every array the analysis reads, copied to the host once (brmi_scene_tables.h: HostScene)
+    HostScene hs; int rc;
+    if ((rc = read_back(p, hs.meshMetadata, sc.meshMetadata, sc.meshMetadataCount))) return rc;
+    if ((rc = read_back(p, hs.clodOffsets, sc.clodOffsets, sc.perMeshInstanceCount))) return rc;
+    if ((rc = read_back(p, hs.lodNodes, sc.lodNodes, sc.lodNodeCount))) return rc;
+    if ((rc = read_back(p, hs.lodSegments, sc.lodSegments, sc.lodSegmentCount))) return rc;
+    if ((rc = read_back(p, hs.openpbrMaterials, sc.openpbrMaterials, sc.openpbrMaterialCount))) return rc;
+    if ((rc = read_back(p, hs.materials, sc.materials, sc.materialCount))) return rc;
+    if ((rc = read_back(p, hs.perMesh, sc.perMesh, sc.perMeshCount))) return rc;
+    if ((rc = read_back(p, hs.perMeshInstance, sc.perMeshInstance, sc.perMeshInstanceCount))) return rc;
+    if ((rc = read_back(p, hs.activeDraws, sc.activeDraws, sc.activeDrawCount))) return rc;
+    if ((rc = read_back(p, hs.groupPageMap, sc.groupPageMap, sc.groupPageMapCount))) return rc;
+    if ((rc = read_back(p, hs.lodGroups, sc.lodGroups, sc.lodGroupCount))) return rc;
+    if ((rc = read_back(p, hs.slabs, sc.slabs, sc.slabCount))) return rc;
+    hs.perObjectCount = sc.perObjectCount; hs.skinningMatrixCount = sc.skinningMatrixCount;      // (nothing reads the contents of perObject or of the matrices)
+    hs.textureTables = sc.textures && sc.samplers && sc.srgbToLinear && sc.textureCount != 0 && sc.samplerCount != 0;
+    const bool flatOn = tuning("flat_traversal", 1) != 0;
+    const bool boxesOn = tuning("hold_clusters", 1) != 0 && p->cfg.enableOcclusionCulling && sc.slabCount <= 4096u;
+    const auto pageMeshlets = [&](uint32_t slab, uint32_t byteOffset, uint32_t* meshlets) -> int { BRMI_HIP(p, hipMemcpy(meshlets, hs.slabs[slab] + byteOffset, 4, hipMemcpyDeviceToHost)); return BRMI_OK; };
+    if ((rc = analyse_scene(hs, flatOn, p->cfg.maxBvhLevels, boxesOn, pageMeshlets, p->tables, p->err))) return rc;
+    // (the interleaved partition keeps the whole list: its compact surfaces hold this GPU's chunks only -- the re-test would have to map rows.  A contiguous band
+    // lives in frame rows: the tests clamp their rectangles to it, and the chain's texels beyond it read "empty")
+    p->holdEnabled = boxesOn && p->tables.totalBoxes != 0u && p->stripes.count <= 1u;
+    p->holdMinClusters = (uint32_t)std::max(0l, tuning("hold_min_clusters", p->holdMinClusters));
+    p->lateDirectMax = (uint32_t)std::max(0l, tuning("late_direct_max", p->lateDirectMax));
+    p->holdStillMax = (uint32_t)std::max(0l, tuning("hold_still_max", p->holdStillMax));
+    p->holdFloor = (uint32_t)std::max(0l, tuning("hold_floor", p->holdFloor));
+    p->holdMaxTexels = (uint32_t)std::min(16l, std::max(1l, tuning("hold_max_texels", p->holdMaxTexels)));
+    p->retestMaxTexels = (uint32_t)std::min(16l, std::max(1l, tuning("retest_max_texels", p->retestMaxTexels)));
+    p->totalWords = (uint32_t)std::max<uint64_t>(1, (p->tables.totalBits + 31) / 32);
     p->scanBlocks = (p->totalWords + 2047u) / 2048u;
-    p->maxLevels = std::min(std::max(1u, maxDepth), std::max(1u, p->cfg.maxBvhLevels));
+    p->maxLevels = std::min(std::max(1u, p->tables.maxDepth), std::max(1u, p->cfg.maxBvhLevels));
     compute_sizes(p);
     p->haveScene = true;
     p->updateSerial++;
@@ -614,14 +402,14 @@ int brmi_setup(brmi_pass* p, const brmi_resource_binding* b, uint32_t n, brmi_st
     // the depth chain starts out "empty" everywhere; a multi-GPU band only ever rewrites the texels its rows reach
     if (p->cfg.enableOcclusionCulling && p->resNeed[BRMI_RES_HZB] >= 4) BRMI_HIP(p, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p->res[BRMI_RES_HZB]), (int)BRMI_DEPTH_EMPTY_BITS, p->resNeed[BRMI_RES_HZB] / 4, s));
     p->hzbValid = false;
-    if (!p->hostInstanceBitBase.empty()) BRMI_HIP(p, hipMemcpyAsync(p->wsPtr<uint32_t>(p->ws.instanceBitBase), p->hostInstanceBitBase.data(), p->hostInstanceBitBase.size() * 4, hipMemcpyHostToDevice, s));
-    if (!p->hostSegPrefix.empty()) BRMI_HIP(p, hipMemcpyAsync(p->wsPtr<uint32_t>(p->ws.segPrefix), p->hostSegPrefix.data(), p->hostSegPrefix.size() * 4, hipMemcpyHostToDevice, s));
-    if (!p->hostMeshLevelWidth.empty()) BRMI_HIP(p, hipMemcpyAsync(p->wsPtr<uint32_t>(p->ws.meshLevelWidth), p->hostMeshLevelWidth.data(), p->hostMeshLevelWidth.size() * 4, hipMemcpyHostToDevice, s));
-    if (!p->hostFlatNodes.empty()) BRMI_HIP(p, hipMemcpyAsync(p->wsPtr<FlatNode>(p->ws.flatNodes), p->hostFlatNodes.data(), p->hostFlatNodes.size() * sizeof(FlatNode), hipMemcpyHostToDevice, s));
-    if (!p->hostFlatLeaves.empty()) BRMI_HIP(p, hipMemcpyAsync(p->wsPtr<FlatLeaf>(p->ws.flatLeaves), p->hostFlatLeaves.data(), p->hostFlatLeaves.size() * sizeof(FlatLeaf), hipMemcpyHostToDevice, s));
-    if (!p->hostInstanceWalk.empty()) BRMI_HIP(p, hipMemcpyAsync(p->wsPtr<InstanceWalk>(p->ws.instanceWalk), p->hostInstanceWalk.data(), p->hostInstanceWalk.size() * sizeof(InstanceWalk), hipMemcpyHostToDevice, s));
-    if (!p->hostPageBoxBase.empty()) BRMI_HIP(p, hipMemcpyAsync(p->wsPtr<uint32_t>(p->ws.pageBoxBase), p->hostPageBoxBase.data(), p->hostPageBoxBase.size() * 4, hipMemcpyHostToDevice, s));
-    if (!p->hostPageRefs.empty()) BRMI_HIP(p, hipMemcpyAsync(p->wsPtr<PageRef>(p->ws.pageRefs), p->hostPageRefs.data(), p->hostPageRefs.size() * sizeof(PageRef), hipMemcpyHostToDevice, s));
+    if (!p->tables.instanceBitBase.empty()) BRMI_HIP(p, hipMemcpyAsync(p->wsPtr<uint32_t>(p->ws.instanceBitBase), p->tables.instanceBitBase.data(), p->tables.instanceBitBase.size() * 4, hipMemcpyHostToDevice, s));
+    if (!p->tables.segPrefix.empty()) BRMI_HIP(p, hipMemcpyAsync(p->wsPtr<uint32_t>(p->ws.segPrefix), p->tables.segPrefix.data(), p->tables.segPrefix.size() * 4, hipMemcpyHostToDevice, s));
+    if (!p->tables.meshLevelWidth.empty()) BRMI_HIP(p, hipMemcpyAsync(p->wsPtr<uint32_t>(p->ws.meshLevelWidth), p->tables.meshLevelWidth.data(), p->tables.meshLevelWidth.size() * 4, hipMemcpyHostToDevice, s));
+    if (!p->tables.flatNodes.empty()) BRMI_HIP(p, hipMemcpyAsync(p->wsPtr<FlatNode>(p->ws.flatNodes), p->tables.flatNodes.data(), p->tables.flatNodes.size() * sizeof(FlatNode), hipMemcpyHostToDevice, s));
+    if (!p->tables.flatLeaves.empty()) BRMI_HIP(p, hipMemcpyAsync(p->wsPtr<FlatLeaf>(p->ws.flatLeaves), p->tables.flatLeaves.data(), p->tables.flatLeaves.size() * sizeof(FlatLeaf), hipMemcpyHostToDevice, s));
+    if (!p->tables.instanceWalk.empty()) BRMI_HIP(p, hipMemcpyAsync(p->wsPtr<InstanceWalk>(p->ws.instanceWalk), p->tables.instanceWalk.data(), p->tables.instanceWalk.size() * sizeof(InstanceWalk), hipMemcpyHostToDevice, s));
+    if (!p->tables.pageBoxBase.empty()) BRMI_HIP(p, hipMemcpyAsync(p->wsPtr<uint32_t>(p->ws.pageBoxBase), p->tables.pageBoxBase.data(), p->tables.pageBoxBase.size() * 4, hipMemcpyHostToDevice, s));
+    if (!p->tables.pageRefs.empty()) BRMI_HIP(p, hipMemcpyAsync(p->wsPtr<PageRef>(p->ws.pageRefs), p->tables.pageRefs.data(), p->tables.pageRefs.size() * sizeof(PageRef), hipMemcpyHostToDevice, s));
     { int rc = launch_expand_luts(p, s); if (rc) return rc; }
     { int rc = launch_meshlet_boxes(p, s); if (rc) return rc; }
     BRMI_HIP(p, hipStreamSynchronize(s));   // host vectors may be reused
@@ -954,7 +742,7 @@ int brmi_execute_split(brmi_pass* p, brmi_stream stream, brmi_stream shadeStream
     p->frameWaitsIssued = true;
     // When the phase-1 traversal is the one-launch LDS walk and the frame constants are due anyway, the frame needs no clear launch: the
     // constants kernel zeroes the culling state and the walk's launch carries the visibility clear (brmi_cull.hip, SideClear).
-    const bool rides = p->constantsSerial != p->updateSerial && p->minLevelWidth <= 1024u /* the one-launch walk runs (brmi_cull.hip: HIER_CAP_MAX) */ && !p->forceLevelKernels && p->scene.activeDrawCount != 0u;
+    const bool rides = p->constantsSerial != p->updateSerial && p->tables.minLevelWidth <= 1024u /* the one-launch walk runs (brmi_cull.hip: HIER_CAP_MAX) */ && !p->forceLevelKernels && p->scene.activeDrawCount != 0u;
     p->lightGridDone = false;
     // A split frame (round 4): the riders move to where they fit -- the visibility clear onto k_cull_clusters' launch (brmi_cull.hip: ClearRide), the
     // light clustering onto the shading stream, which is idle until this frame's pixel pass (below, behind the same event as the early resolve setup).
@@ -1130,7 +918,7 @@ int brmi_algorithmic_bytes(brmi_pass* p, uint64_t* perStage, uint64_t* total) {
 
 int brmi_algorithmic_bytes_launched(brmi_pass* p, uint64_t* perStage, uint64_t* total) {
     if (int rc = brmi_algorithmic_bytes(p, perStage, total)) return rc;
-    if (!p->sceneHasCoat && !p->sceneHasFuzz) {      // k_shade<0>: depth 4 + normals 16 + albedo 4 + metallic / roughness 4 + emissive 8 read, HDR 8 written; the coat and fuzz planes (8 + 8) stay unread
+    if (!p->tables.hasCoat && !p->tables.hasFuzz) {      // k_shade<0>: depth 4 + normals 16 + albedo 4 + metallic / roughness 4 + emissive 8 read, HDR 8 written; the coat and fuzz planes (8 + 8) stay unread
         const uint64_t P = (uint64_t)p->cfg.width * (p->bandY1 - p->bandY0);
         *total -= perStage[BRMI_STAGE_SHADE]; perStage[BRMI_STAGE_SHADE] = 44ull * P; *total += perStage[BRMI_STAGE_SHADE];
     }

@@ -1674,24 +1674,24 @@ int launch_cull(brmi_pass* p, uint32_t phase, hipStream_t s) {
     bool lightGridRides = false;      // this call's launches carry the light clustering (brmi_execute)
     bool flatLevels = false;          // phase 1 ran the level-synchronous flat traversal: nothing is left for the walk or the level kernels
     // one launch of k_cull_hierarchy for the meshes that fit its LDS frontier, the level kernels for the rest (or for everything: tests)
-    const bool hierarchy = p->minLevelWidth <= HIER_CAP_MAX && !p->forceLevelKernels;
-    const bool levelKernels = p->maxLevelWidth > p->spillWidth || p->forceLevelKernels;
+    const bool hierarchy = p->tables.minLevelWidth <= HIER_CAP_MAX && !p->forceLevelKernels;
+    const bool levelKernels = p->tables.maxLevelWidth > p->tables.spillWidth || p->forceLevelKernels;
     const uint32_t* meshWidth = p->wsPtr<uint32_t>(p->ws.meshLevelWidth);
     // meshes of both kinds: the one-launch walk also starts the wide ones and hands their frontiers to the level kernels (spill mode)
     const bool spillMode = hierarchy && levelKernels;
     a.meshLevelWidth = meshWidth; a.levelKernelsWidthLo = 0u;
     if (spillMode) a.frontier0Counter = CNT_FRONTIER0;
-    const uint32_t widthAll = spillMode ? 0xFFFFFFFFu : 0u, spillAbove = spillMode ? p->spillWidth : 0xFFFFFFFFu;
+    const uint32_t widthAll = spillMode ? 0xFFFFFFFFu : 0u, spillAbove = spillMode ? p->tables.spillWidth : 0xFFFFFFFFu;
     if (phase == 1) {
         if (!p->frameStateCleared) BRMI_HIP(p, hipMemsetAsync(p->counters(), 0, p->ws.frameClearBytes, s));      // counters + both survivor bitmasks
         p->frameStateCleared = false;
         // (CLodStreamingBeginFramePass: the frame's touched bits and best requests start from zero)
         if (p->streaming.on) BRMI_HIP(p, hipMemsetAsync(p->streaming.b.scratch, 0, stream_scratch_layout(p->streaming.groupCount).frameBytes, s));
-        // (the first ceil(draws / 8) waves of the walk take eight draws each: hierarchies of <= 8 nodes, the flat tables of brmi_set_scene)
-        a.packedFlat = (hierarchy && !p->hostFlatNodes.empty() && p->packedFlat) ? 1u : 0u;
+        // (the first ceil(draws / 8) waves of the walk take eight draws each: hierarchies of <= 8 nodes, the flat tables of build_flat_tables (brmi_scene_tables.h))
+        a.packedFlat = (hierarchy && !p->tables.flatNodes.empty() && p->packedFlat) ? 1u : 0u;
         // (not beside another frame's shading half: a 1024-thread workgroup with 40 KB of LDS waits long for a CU that can take it, and the
         // dense frame in flight went 0.795 -> 0.91 ms; alone the same frame's cull stage goes 0.180 -> 0.142 ms)
-        a.wideFlat = (hierarchy && p->anyWideFlat && !p->splitFrame) ? 1u : 0u;
+        a.wideFlat = (hierarchy && p->tables.anyWideFlat && !p->splitFrame) ? 1u : 0u;
         // Scenes of very many draws (Zorah-class): the level-synchronous flat traversal, a lane per (instance, node) task, one launch per level of the
         // deepest hierarchy (k_cull_flat_level).  Its launches carry no riders: the visibility clear moves onto k_cull_clusters (ClearRide) and the
         // light clustering is launched by the frame where it finds none done.
@@ -1699,7 +1699,7 @@ int launch_cull(brmi_pass* p, uint32_t phase, hipStream_t s) {
         // and 24 KB of LDS find few slots beside another frame's shading waves -- San-Miguel-class, 7,577 draws: 0.848 -> 0.823 ms in flight although the stage alone is 0.107 -> 0.119;
         // the dense and Bistro-class frames, with fewer draws, lose either way)
         const uint32_t draws = p->scene.activeDrawCount, minDraws = std::max(1u, p->flatLevelsMinDraws);
-        flatLevels = hierarchy && p->allMeshesFlat && !p->forceLevelKernels && (draws >= minDraws || (p->splitFrame && p->maxLevelWidth > 256u && draws >= std::max(1u, minDraws / 4u)));
+        flatLevels = hierarchy && p->tables.allMeshesFlat && !p->forceLevelKernels && (draws >= minDraws || (p->splitFrame && p->tables.maxLevelWidth > 256u && draws >= std::max(1u, minDraws / 4u)));
         if (flatLevels) {
             if (p->clearVisibilityWithTraversal && (p->bandPixelCount & 1ull) == 0ull) { p->clearVisibilityWithTraversal = false; p->clearVisibilityWithClusterCull = true; }
             else if (p->clearVisibilityWithTraversal) flatLevels = false;      // (an odd pixel count: the riding clear of the walk handles it)
@@ -1707,7 +1707,7 @@ int launch_cull(brmi_pass* p, uint32_t phase, hipStream_t s) {
         if (flatLevels) {
             with_residency([&](auto res) { hipLaunchKernelGGL((k_cull_flat_level<true, decltype(res)>), dim3(grid_for(p->scene.activeDrawCount, 256, 8192)), dim3(256), 0, s, a, 0u, (const NodeRecord*)nullptr, fb, buckets, res); });
             // (frontier sizes live on the device; every level strides a fixed grid and a workgroup that finds none of its tasks leaves after one load)
-            for (uint32_t level = 1; level < p->flatMaxDepth; level++)
+            for (uint32_t level = 1; level < p->tables.flatMaxDepth; level++)
                 with_residency([&](auto res) { hipLaunchKernelGGL((k_cull_flat_level<false, decltype(res)>), dim3(2048), dim3(256), 0, s, a, level, (const NodeRecord*)((level & 1u) ? fb : fa), (level & 1u) ? fa : fb, buckets, res); });
             BRMI_LAUNCH_CHECK(p, "k_cull_flat_level");
         }
@@ -1715,7 +1715,7 @@ int launch_cull(brmi_pass* p, uint32_t phase, hipStream_t s) {
         if (hierarchy && !flatLevels) {
             // ONE launch: the 6 KB-frontier variant when every mesh is narrow (<= 256 nodes per level), else the 24 KB variant for all meshes up
             // to 1024 (two launches, one per class, ran one after the other: San-Miguel-class cull 178 -> 140 us with one)
-            const bool wide = p->maxLevelWidth > 256u;
+            const bool wide = p->tables.maxLevelWidth > 256u;
             const uint32_t widthHi = spillMode ? widthAll : (wide ? HIER_CAP_MAX : 256u);
             if (p->clearVisibilityWithTraversal) {
                 SideJobs sj{reinterpret_cast<ulonglong2*>(static_cast<unsigned long long*>(p->res[BRMI_RES_VISIBILITY]) + p->bandFirstPixel), p->bandPixelCount >> 1, hgrid.x, p->clearRiderBlocks, cluster_args_of(p)};
@@ -1734,14 +1734,14 @@ int launch_cull(brmi_pass* p, uint32_t phase, hipStream_t s) {
         if (!p->phase2Seeded) hipLaunchKernelGGL(k_seed_phase2, dim3(1), dim3(128), 0, s, p->counters(), a.recordCapacity);
         p->phase2Seeded = false;
         const NoSide none{};
-        if (hierarchy && p->maxLevelWidth <= 256u) with_residency([&](auto res) { hipLaunchKernelGGL((k_cull_hierarchy<true, 256, 128, false, decltype(res)>), dim3(2048), dim3(64), 0, s, a, buckets, meshWidth, 0u, 256u, spillAbove, fa, none, res); });
+        if (hierarchy && p->tables.maxLevelWidth <= 256u) with_residency([&](auto res) { hipLaunchKernelGGL((k_cull_hierarchy<true, 256, 128, false, decltype(res)>), dim3(2048), dim3(64), 0, s, a, buckets, meshWidth, 0u, 256u, spillAbove, fa, none, res); });
         else if (hierarchy) with_residency([&](auto res) { hipLaunchKernelGGL((k_cull_hierarchy<true, 1024, BRMI_HIER_STAGE_WIDE, false, decltype(res)>), dim3(2048), dim3(64), 0, s, a, buckets, meshWidth, 0u, spillMode ? widthAll : HIER_CAP_MAX, spillAbove, fa, none, res); });
     }
     // frontier sizes are only known on the device: size the grids for the worst case that can matter
     const uint32_t travGrid = grid_for(std::min<uint64_t>(p->cfg.maxTraversalRecords, (uint64_t)p->scene.lodNodeCount * 4 + 4096), 256, maxBlocks);
-    const uint32_t levelLaunches = spillMode ? std::min(p->maxLevels, std::max(1u, p->spillLevels)) : p->maxLevels;
+    const uint32_t levelLaunches = spillMode ? std::min(p->maxLevels, std::max(1u, p->tables.spillLevels)) : p->maxLevels;
     // (phase 1 of a scene whose every hierarchy is evaluated flat leaves nothing for the level kernels)
-    const bool flatCoversPhase1 = phase == 1 && hierarchy && spillMode && p->allMeshesFlat && a.wideFlat != 0u && !p->forceLevelKernels;
+    const bool flatCoversPhase1 = phase == 1 && hierarchy && spillMode && p->tables.allMeshesFlat && a.wideFlat != 0u && !p->forceLevelKernels;
     for (uint32_t level = 0; level < levelLaunches && levelKernels && !flatCoversPhase1 && !flatLevels; level++) {
         // without the walk in front (forced level kernels) phase 2 reads level 0 from the replay buffer; then ping-pong like phase 1 (level 0 writes fb)
         const NodeRecord* in = level == 0 ? ((phase == 1 || spillMode) ? fa : a.replayNodes) : ((level & 1u) ? fb : fa);
@@ -1795,7 +1795,7 @@ int launch_cull(brmi_pass* p, uint32_t phase, hipStream_t s) {
     auto scatter = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(scatterGrid), dim3(256), 0, s, temp, p->counters(), (uint32_t)(phase == 1 ? CNT_TEMP_VISIBLE : CNT_TEMP_VISIBLE2), bitmask, wordPrefix,
                            static_cast<uint4*>(p->res[BRMI_RES_VISIBLE_CLUSTERS]), phase == 1 ? 0xFFFFFFFFu : (uint32_t)CNT_VISIBLE, p->cfg.maxVisibleClusters, p->cfg.maxVisibleClusters, p->scene, p->wsPtr<ClusterSetup>(p->ws.clusterSetup), arenaCapacity,
-                           (p->sceneHasTextures || p->sceneHasAlphaTest || p->sceneHasVertexColors) ? p->wsPtr<ClusterUv>(p->ws.clusterUv) : nullptr, LocalRank{p->totalWords, outIndex, usedIndex, feedback},
+                           (p->tables.hasTextures || p->tables.hasAlphaTest || p->tables.hasVertexColors) ? p->wsPtr<ClusterUv>(p->ws.clusterUv) : nullptr, LocalRank{p->totalWords, outIndex, usedIndex, feedback},
                            (phase == 1 && p->holdThisFrame) ? DrawLists{p->wsPtr<uint32_t>(p->ws.drawList), p->wsPtr<HeldRecord>(p->ws.heldRecords), 0u, p->wsPtr<MeshletBox>(p->ws.meshletBoxes), p->wsPtr<uint32_t>(p->ws.pageBoxBase),
                                                                       p->wsPtr<float>(p->ws.objConst), p->holdMaxTexels, BoxViewport{(float)p->cfg.width, (float)p->cfg.height, 0.0f, 0.0f, 0, (int)p->bandY0, (int)p->cfg.width - 1, (int)p->bandY1 - 1}, a.hzb}
                                                           : DrawLists{nullptr, nullptr, p->holdThisFrame ? 1u : 0u, nullptr, nullptr, nullptr, 0u, BoxViewport{}, HzbDesc{}});
@@ -1837,8 +1837,8 @@ __global__ void __launch_bounds__(256) k_meshlet_boxes(const uint8_t* const* sla
 }
 
 int launch_meshlet_boxes(brmi_pass* p, hipStream_t s) {
-    if (p->hostPageRefs.empty()) return BRMI_OK;
-    hipLaunchKernelGGL(k_meshlet_boxes, dim3((uint32_t)p->hostPageRefs.size()), dim3(256), 0, s, p->scene.slabs, p->wsPtr<PageRef>(p->ws.pageRefs), p->wsPtr<MeshletBox>(p->ws.meshletBoxes));
+    if (p->tables.pageRefs.empty()) return BRMI_OK;
+    hipLaunchKernelGGL(k_meshlet_boxes, dim3((uint32_t)p->tables.pageRefs.size()), dim3(256), 0, s, p->scene.slabs, p->wsPtr<PageRef>(p->ws.pageRefs), p->wsPtr<MeshletBox>(p->ws.meshletBoxes));
     BRMI_LAUNCH_CHECK(p, "k_meshlet_boxes");
     return BRMI_OK;
 }

@@ -279,7 +279,7 @@ int ensure_frame_constants(brmi_pass* p, hipStream_t s) {
     j.sc = p->scene; j.frameConst = p->wsPtr<m4>(p->ws.frameConst); j.snapshot = p->wsPtr<FrameSnapshot>(p->ws.frameSnapshot); j.objConst = p->wsPtr<float>(p->ws.objConst);
     j.matWords = p->wsPtr<MaterialWords>(p->ws.matWords); j.matConst = p->wsPtr<MatConst>(p->ws.matConst); j.tables = shade_tables_of(p);
     j.lightVS = p->wsPtr<float4>(p->ws.lightVS); j.lightMeta = p->wsPtr<uint32_t>(p->ws.lightMeta); j.shadeLights = p->wsPtr<float4>(p->ws.shadeLights);
-    j.alphaMats = p->sceneHasAlphaTest ? p->wsPtr<AlphaMaterial>(p->ws.alphaMats) : nullptr;
+    j.alphaMats = p->tables.hasAlphaTest ? p->wsPtr<AlphaMaterial>(p->ws.alphaMats) : nullptr;
     j.layer = p->wsPtr<LayerUniform>(p->ws.layerUniform);
     j.W = p->cfg.width; j.H = p->cfg.height; j.stripes = p->stripes;
     for (int k = 0; k < 3; k++) { j.bandPlanes[k] = p->bandPlaneTop[k]; j.bandPlanes[4 + k] = p->bandPlaneBottom[k]; }

@@ -9,6 +9,7 @@
 
 #include "brmi.h"
 #include "brmi_device.h"
+#include "brmi_scene_tables.h"
 
 #ifndef BRMI_BIN_COUNT_STRIDE
 #define BRMI_BIN_COUNT_STRIDE 32      // words between the record counters of two raster bins (brmi_raster.hip)
@@ -37,8 +38,7 @@ enum CounterIndex : uint32_t {
     CNT_RESERVED_37,          // (round 4's "clusters marked" flag; the slot keeps the enumeration's layout)
     CNT_DEFERRED_DROPPED,     // layered pixels that found their deferred-list stripe full (impossible by construction; counted anyway)
     CNT_TILE_OVERFLOW,        // (cluster, tile) pairs of the tile rasteriser that found the tile's list full (folded into CNT_BIN_OVERFLOW per phase)
-    CNT_FRONTIER0 = 32,       // frontier sizes per BFS level: [CNT_FRONTIER0 + level]
-    CNT_STRIPES = 128,        // 64 stripes x 32 words: per-stripe {instances tested, instances visible, nodes visited}
+    // (CNT_FRONTIER0 and CNT_STRIPES, the per-level frontier sizes and the stripe statistics between this group and the next: brmi_scene_tables.h, whose flat tables they bound)
     CNT_STRIPE_COUNT = 64, CNT_STRIPE_WORDS = 32,
     STRIPE_DEFERRED_A = 4, STRIPE_DEFERRED_B = 8,   // words of a stripe: deferred-pixel list lengths (3 classes each) of alternating shading calls
     STRIPE_OVERFLOW = 3,      // word of a stripe: records in the stripe's raster overflow queue
@@ -75,24 +75,7 @@ __device__ inline void seed_phase2(uint32_t* counters, uint32_t capacity, uint32
     }
 }
 
-// internal records (ours; the reference's 12 B / 24 B records plus the rank bookkeeping)
-// A mesh whose whole BVH has at most 8192 nodes (brmi_set_scene walks it) is evaluated flat by the traversal kernels: one lane per node (a wave for
-// up to 256 nodes, eight draws to a wave up to 8, a 1024-thread workgroup beyond 256), the
-// records below instead of the node -> group / segment chain (static topology: node, group and segment contents as brmi_set_scene read them;
-// what the host may rewrite between frames -- instances, objects, the page map -- is still read from its buffers).
-struct FlatNode {                                                                     // 64 B, breadth-first (a parent's position is below its children's)
-    float cull[4], lod[4]; float maxQuadricError;
-    uint32_t nodeId;            // relative to the mesh's lodNodesBase (replay records name nodes by it)
-    uint32_t info;              // internal | has a refined group << 1 | segment holds meshlets << 2 | parent position << 8 (breadth-first: below the node's own)
-    uint32_t ownerGroup;        // leaf: mesh-local group
-    uint32_t segFirstCount;     // leaf: firstMeshletInPage | meshletCount << 16
-    uint32_t pageMapIndex;      // leaf: absolute index of the segment's page-map entry
-    uint32_t firstBitRel;       // leaf: the segment's first bit relative to the instance's
-    uint32_t children;          // internal: position of the first child | child count << 16 (breadth-first: a node's children sit side by side)
-};
-struct FlatLeaf { float group[4], child[4]; float childParentError; uint32_t ownerGlobal, childGlobal /* indices into lodGroups: what the residency rule looks up (brmi_set_streaming) */, pad; };      // 48 B: the leaf's group sphere, its refined group's sphere and error
-struct InstanceWalk { uint32_t flatBase, flatCount /* 0: the level walk */, bitBase, skinned; };                                    // 16 B per mesh instance
-static_assert(sizeof(FlatNode) == 64 && sizeof(FlatLeaf) == 48 && sizeof(InstanceWalk) == 16, "flat traversal records");
+// internal records (ours; the flat traversal records and PageRef: brmi_scene_tables.h)
 struct NodeRecord { uint32_t instanceIndex, nodeIdPacked; };                       // 8 B (single view)
 struct BucketRecord {                                                                 // 32 B
     uint32_t instanceIndex, groupIdPacked, meshletIndexAndCount, pageSlabDescriptorIndex;
@@ -102,9 +85,8 @@ struct TempVisible { uint4 packed; uint32_t bit, pad0, pad1, pad2; };           
 // Round 6: what the library keeps per meshlet BESIDE the reference's descriptor (whose only bound is a sphere): the object-space box of its vertices, made once per
 // brmi_setup from the page contents (k_meshlet_boxes).  Not part of the data contract; indexed by pageBoxBase[slab * 1024 + page] + meshlet.
 struct MeshletBox { float lo[3]; uint32_t valid; float hi[3]; uint32_t pad; };       // 32 B
-struct PageRef { uint32_t slab, byteOffset, boxBase, meshletCount; };                 // one resident page (brmi_set_scene walks the page map)
 struct HeldRecord { uint32_t clusterIndex, boxIndex, perObjectIndex, vertsTris /* vertices | triangles << 16 */; };   // 16 B: a visible cluster the phase-1 rasteriser does not take until the re-test has looked at it
-static_assert(sizeof(MeshletBox) == 32 && sizeof(PageRef) == 16 && sizeof(HeldRecord) == 16, "draw-list records");
+static_assert(sizeof(MeshletBox) == 32 && sizeof(HeldRecord) == 16, "draw-list records");
 constexpr uint32_t OBJ_CONST_FLOATS = 56;      // per object: MVP (16), objectToClip (16), modelViewZ (4), previous frame's MVP (16) and modelViewZ (4)
 
 // Everything the rasteriser and the G-buffer pass need to start on a visible cluster, resolved once by the compaction
@@ -305,13 +287,8 @@ struct brmi_pass {
     float bandPlaneTop[3] = {0, 0, 0}, bandPlaneBottom[3] = {0, 0, 0};
     uint64_t bandFirstPixel = 0, bandPixelCount = 0;   // tiled index range covering the band's tile rows
     uint32_t maxLevels = 1;
-    static constexpr uint32_t spillWidth = 1024;      // meshes with a BVH level wider than this go to the level kernels below their top (<= the widest LDS frontier)
-    uint32_t spillLevels = 0;        // level-kernel launches the widest meshes still need below the point where the LDS walk hands them over
-    uint32_t minLevelWidth = 0;      // narrowest such width over the meshes
-    std::vector<uint32_t> hostMeshLevelWidth;   // per mesh metadata entry
-    uint32_t maxLevelWidth = 0;      // widest BVH level of any mesh (decides between the per-instance and the per-level traversal)
-    // Round 6, the draw list: per-meshlet boxes of the scene's resident pages and whether this pass holds clusters back (brmi_raster.hip)
-    std::vector<brmi::PageRef> hostPageRefs; std::vector<uint32_t> hostPageBoxBase; uint32_t totalBoxes = 0;
+    brmi::SceneTables tables;        // everything derived from the scene's arrays (brmi_set_scene -> brmi_scene_tables.h: analyse_scene); uploaded by brmi_setup
+    // Round 6, the draw list: whether this pass holds clusters back (brmi_raster.hip)
     bool holdEnabled = false;        // the pass can hold clusters back: occlusion culling on, no band / interleaved partition, boxes available (BRMI_TUNING hold_clusters=0: off)
     bool holdThisFrame = false;      // this frame's phase 1 made a draw list (launch_cull -> launch_raster)
     uint32_t holdMinClusters = 16384; // hold only on frames whose last known visible-cluster count is at least this (BRMI_TUNING hold_min_clusters): below it the re-test, the late
@@ -335,10 +312,6 @@ struct brmi_pass {
     bool leanActive = false, leanLastLaunch = false; uint32_t leanRetryIn = 0;
     uint32_t wideMinTriangles = 4;   // the wide pass is launched while the last frame the host has seen queued at least this many (BRMI_TUNING wide_min_triangles)
     bool chainBuiltInRaster = false; // this frame's phase-1 rasteriser stage built the chain itself (before its re-test): the build that follows redoes the late pass's blocks only
-    bool sceneHasVertexColors = false;                           // some mesh's pages carry vertex colours (perMesh.vertexFlags bit 0)
-    uint32_t sceneUvSets = 1;      // UV sets the texture slots of the scene's materials name (brmi_set_scene)
-    bool sceneHasAlphaTest = false, sceneHasTextures = false, sceneHasParallax = false;   // some material is alpha tested / samples a texture (brmi_set_scene)
-    bool sceneHasCoat = true, sceneHasFuzz = true;   // some OpenPBR material has a coat / fuzz layer (brmi_set_scene)
     std::vector<float> sliceStartHost; float sliceKey[3] = {0, 0, 0}; uint32_t sliceKeyN[2] = {0, 0};   // slice starts of the light-cluster grid and the inputs they were made from
     // Phase 2 of a frame usually draws nothing or a few dozen clusters; then its triangles all take the row re-deal with global atomics (one
     // launch instead of k_raster + plan + bins).  Which it is, the host learns from the frames before: the ranking kernel of phase 2 also stores
@@ -359,8 +332,6 @@ struct brmi_pass {
     bool splitFrame = false;         // brmi_execute_split with two streams: this frame's launches share the chip with another frame's
     uint32_t shadeSlabs = 0; brmi_slab_fn shadeSlabFn = nullptr; void* shadeSlabUser = nullptr;      // brmi_set_shade_slabs
     bool frameWaitsIssued = false;   // brmi_execute_split has issued this frame's cross-stream waits (the stage entry points it calls skip theirs)
-    bool anyWideFlat = false, allMeshesFlat = false;      // brmi_set_scene: some mesh has 257 .. 8192 nodes / every mesh has flat tables
-    uint32_t flatMaxDepth = 1;       // levels of the deepest flat hierarchy (launches of the level-synchronous flat traversal, brmi_cull.hip: k_cull_flat_level)
     uint32_t flatLevelsMinDraws = 16384;   // BRMI_FLAT_LEVELS_MIN_DRAWS: scenes with at least this many draws (all hierarchies flat) take the level-synchronous flat traversal in phase 1
     uint32_t scanEpoch = 0;          // k_scan_chained (the survivor ranking as one launch): its block sums carry this launch count
     bool packedFlat = true;          // BRMI_FLAT_PACKED=0: one draw per wave of the traversal
@@ -373,7 +344,7 @@ struct brmi_pass {
     bool seedInHzbTail = false, phase2Seeded = false;           // brmi_execute: the tail of the phase-1 depth-chain build also seeds phase 2 (k_seed_phase2's work)
     bool fuseFrameClear = false, frameStateCleared = false;   // brmi_execute: the visibility clear also clears the culling pass's frame state
     bool forceLevelKernels = false;  // BRMI_CULL_LEVEL_KERNELS=1: always use the per-level kernels (tests, very wide hierarchies)
-    uint64_t totalBits = 0; uint32_t totalWords = 0, scanBlocks = 0;
+    uint32_t totalWords = 0, scanBlocks = 0;      // words of the survivor bitmask (tables.totalBits) and its 2048-word scan blocks
     uint32_t numLightClusters = 0, lightPagePool = 0;
     uint32_t binOverflowPerStripe = 1u << 14;       // 64 stripes x 16384 records x 64 B = 64 MB
     uint32_t binMinSlice = 1024, binSharedSlice = 512, binGrid = 1024;   // k_raster_bins: records one workgroup walks alone / per slice of a larger bin, workgroups of the pool (BRMI_BIN_MIN_SLICE, BRMI_BIN_SHARED_SLICE, BRMI_BIN_GRID)
@@ -406,8 +377,6 @@ struct brmi_pass {
     bool depthFinal = false;         // brmi_execute: the depth map is final before the G-buffer kernel runs (it skips its depth store)
     const brmi_pass* chainOwner(uint32_t phase) const { return (phase == 1 && history) ? history : this; }
     brmi::HzbDesc hzbDesc() const;
-    std::vector<uint32_t> hostInstanceBitBase, hostSegPrefix;
-    std::vector<brmi::FlatNode> hostFlatNodes; std::vector<brmi::FlatLeaf> hostFlatLeaves; std::vector<brmi::InstanceWalk> hostInstanceWalk;   // flat traversal tables (brmi_set_scene)
     brmi::Workspace ws{};
     struct { bool on = false; brmi_streaming_buffers b{}; uint32_t groupCount = 0, activeGroupScanCount = 0; } streaming;      // brmi_set_streaming (cleared by brmi_set_scene)
     struct { bool on = false; brmi_debug_view_buffers b{}; } debugView;      // brmi_set_debug_view

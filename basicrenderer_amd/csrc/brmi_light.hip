@@ -213,7 +213,7 @@ ShadeArgs shade_args_of(brmi_pass* p) {
     a.lutF = p->wsPtr<float>(p->ws.lutF);
     a.matConst = p->wsPtr<MatConst>(p->ws.matConst);
     a.shadeRows = p->wsPtr<ShadeRows>(p->ws.shadeRows); a.shadeAvgs = p->wsPtr<ShadeAverages>(p->ws.shadeAvgs); a.ggxQuads = p->wsPtr<GgxQuad>(p->ws.ggxQuads);
-    a.sceneHasCoat = p->sceneHasCoat ? 1u : 0u;
+    a.sceneHasCoat = p->tables.hasCoat ? 1u : 0u;
     a.tables = shade_tables_of(p);
     a.counters = p->counters(); a.deferred = p->wsPtr<uint32_t>(p->ws.deferredPixels);
     a.deferredWord = (p->shadeSerial & 1u) ? STRIPE_DEFERRED_B : STRIPE_DEFERRED_A;
@@ -255,18 +255,18 @@ static int launch_shade_range(brmi_pass* p, hipStream_t s, uint32_t row0, uint32
     if (p->env.on) {
         if (p->shadeSharesChip) hipLaunchKernelGGL((k_shade_ibl<0, BRMI_SHADE_WAVES>), dim3(std::max(256u, p->shadeGridShared / share)), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((k_shade_ibl<0, BRMI_SHADE_WAVES_ALONE>), dim3(std::max(256u, 8192u / share)), dim3(256), 0, s, a);
-        if (p->sceneHasCoat) hipLaunchKernelGGL(k_shade_ibl<1>, dim3(512), dim3(256), 0, s, a);
-        if (p->sceneHasFuzz) hipLaunchKernelGGL(k_shade_ibl<2>, dim3(512), dim3(256), 0, s, a);
-        if (p->sceneHasCoat && p->sceneHasFuzz) hipLaunchKernelGGL(k_shade_ibl<3>, dim3(512), dim3(256), 0, s, a);
+        if (p->tables.hasCoat) hipLaunchKernelGGL(k_shade_ibl<1>, dim3(512), dim3(256), 0, s, a);
+        if (p->tables.hasFuzz) hipLaunchKernelGGL(k_shade_ibl<2>, dim3(512), dim3(256), 0, s, a);
+        if (p->tables.hasCoat && p->tables.hasFuzz) hipLaunchKernelGGL(k_shade_ibl<3>, dim3(512), dim3(256), 0, s, a);
         BRMI_LAUNCH_CHECK(p, "k_shade_ibl");
         return BRMI_OK;
     }
     if (p->shadeSharesChip) hipLaunchKernelGGL((k_shade<0, BRMI_SHADE_WAVES>), dim3(std::max(256u, p->shadeGridShared / share)), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((k_shade<0, BRMI_SHADE_WAVES_ALONE>), dim3(std::max(256u, 8192u / share)), dim3(256), 0, s, a);
     // deferred pixels by class: coat, fuzz, both -- only the variants some material of the scene can need
-    if (p->sceneHasCoat) hipLaunchKernelGGL(k_shade<1>, dim3(512), dim3(256), 0, s, a);
-    if (p->sceneHasFuzz) hipLaunchKernelGGL(k_shade<2>, dim3(512), dim3(256), 0, s, a);
-    if (p->sceneHasCoat && p->sceneHasFuzz) hipLaunchKernelGGL(k_shade<3>, dim3(512), dim3(256), 0, s, a);
+    if (p->tables.hasCoat) hipLaunchKernelGGL(k_shade<1>, dim3(512), dim3(256), 0, s, a);
+    if (p->tables.hasFuzz) hipLaunchKernelGGL(k_shade<2>, dim3(512), dim3(256), 0, s, a);
+    if (p->tables.hasCoat && p->tables.hasFuzz) hipLaunchKernelGGL(k_shade<3>, dim3(512), dim3(256), 0, s, a);
     BRMI_LAUNCH_CHECK(p, "k_shade");
     return BRMI_OK;
 }

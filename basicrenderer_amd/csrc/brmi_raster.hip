@@ -1517,7 +1517,7 @@ int launch_raster(brmi_pass* p, uint32_t phase, hipStream_t s) {
     a.bigTriArea = p->bigTriArea; a.bigTriAreaAlpha = p->bigTriAreaAlpha;
     a.bigTriAreaDense = p->bigTriAreaDense; a.denseClusterCount = p->denseClusterCount;
     // alpha-tested scenes: a slice's alpha records all go through the task list of k_raster_bins<true> (BRMI_ALPHA_LIST entries), so no slice is longer than that
-    a.binMinSlice = p->sceneHasAlphaTest ? std::min(p->binMinSlice, (uint32_t)BRMI_ALPHA_LIST) : p->binMinSlice;
+    a.binMinSlice = p->tables.hasAlphaTest ? std::min(p->binMinSlice, (uint32_t)BRMI_ALPHA_LIST) : p->binMinSlice;
     a.binSharedSlice = std::max(32u, std::min(p->binSharedSlice, a.binMinSlice) & ~31u);        // a multiple of the 32 records a step walks: no slice of the plan is empty
     a.binPlan = p->wsPtr<uint32_t>(p->ws.binPlan); a.binItems = p->wsPtr<uint32_t>(p->ws.binItems); a.binScratch = p->wsPtr<unsigned long long>(p->ws.binScratch);
     a.binScratchTiles = p->binScratchTiles; a.binItemCapacity = p->binItemCapacity;
@@ -1527,8 +1527,8 @@ int launch_raster(brmi_pass* p, uint32_t phase, hipStream_t s) {
     a.clusterUv = p->wsPtr<ClusterUv>(p->ws.clusterUv);
     a.alphaMats = p->wsPtr<AlphaMaterial>(p->ws.alphaMats);
     // (k_raster_bins<true> packs the material index of a waiting pixel with its 12-bit tile cell into one word)
-    if (p->sceneHasAlphaTest && p->scene.materialCount > (1u << 20)) return fail(p, BRMI_ERR_INVALID, "brmi_raster: %u materials in a scene with alpha-tested ones (at most %u)", p->scene.materialCount, 1u << 20);
-    if (p->sceneHasAlphaTest) if (int rc = ensure_frame_constants(p, s)) return rc;
+    if (p->tables.hasAlphaTest && p->scene.materialCount > (1u << 20)) return fail(p, BRMI_ERR_INVALID, "brmi_raster: %u materials in a scene with alpha-tested ones (at most %u)", p->scene.materialCount, 1u << 20);
+    if (p->tables.hasAlphaTest) if (int rc = ensure_frame_constants(p, s)) return rc;
     // the pool of k_raster_bins: four 512-thread workgroups per CU is what the LDS holds; phase 2 rarely has an item at all
     // Round 4: phase-2 launches are sized by what the host last saw phase 2 draw (the host-mapped word of the ranking kernel, read without a wait: a frame
     // or two old; every kernel here strides its grid or takes items by ticket, so any size gives the same keys).  Beside another frame's shading half a
@@ -1547,14 +1547,14 @@ int launch_raster(brmi_pass* p, uint32_t phase, hipStream_t s) {
     // limit the three launches pay (1,000 clusters: raster2 0.068 against 0.121 ms).  Either way the same keys.
     // (not in scenes with alpha-tested materials: a tested pixel costs three times as much through the global chain as in a bin, and the
     // San-Miguel-class camera path got 9 % slower with 19 phase-2 clusters per frame)
-    const bool direct2 = phase == 2 && !p->sceneHasAlphaTest && p->phase2FeedbackHost && *reinterpret_cast<volatile uint32_t*>(p->phase2FeedbackHost) <= p->phase2DirectMax && p->phase2DirectMax != 0u;
+    const bool direct2 = phase == 2 && !p->tables.hasAlphaTest && p->phase2FeedbackHost && *reinterpret_cast<volatile uint32_t*>(p->phase2FeedbackHost) <= p->phase2DirectMax && p->phase2DirectMax != 0u;
     if (direct2) a.bigTriArea = a.bigTriAreaAlpha = a.bigTriAreaDense = 0x3FFFFFFF;
     // phase 2 rarely has more than a handful of clusters: 2048 workgroups (the kernel strides; two waves per SIMD) start and retire a little
     // faster than 8192 that find nothing (-3 us per frame)
     constexpr uint32_t grid2 = 2048;
     const dim3 rgrid(phase == 2 ? std::min(p->rasterGrid, sized2 ? std::max(128u, std::min(grid2, pow2_at_least(hint2 * 16u))) : grid2) : p->rasterGrid);
     const dim3 ogrid(phase == 2 && sized2 ? std::max(2u, std::min(129u, hint2 / 4u + 2u)) : 129u);      // (block 0 plans the bins launch; the others walk the overflow queues)
-    if (p->sceneHasAlphaTest) {
+    if (p->tables.hasAlphaTest) {
         hipLaunchKernelGGL(k_raster<true>, rgrid, dim3(64), a.tableCells * 4u, s, a);
         if (!direct2 && wideOn) hipLaunchKernelGGL(k_raster_wide<true>, wgrid, dim3(64), 0, s, a);
         if (!direct2) hipLaunchKernelGGL(k_raster_overflow<true>, ogrid, dim3(256), 0, s, a);
@@ -1615,10 +1615,10 @@ int launch_raster(brmi_pass* p, uint32_t phase, hipStream_t s) {
         p->chainDirtyTracked = l.chainDirty != nullptr; p->chainBuiltInRaster = true;
         // few late clusters (a still or slowly moving camera: the prediction and the re-test ask the same question of nearly the same depth): every triangle through the
         // row re-deal with global atomics, ONE launch, as the small phase 2; many: records, plan and bins once more
-        const bool directLate = lastLate <= (p->sceneHasAlphaTest ? 0u : p->lateDirectMax);
+        const bool directLate = lastLate <= (p->tables.hasAlphaTest ? 0u : p->lateDirectMax);
         if (directLate) l.bigTriArea = l.bigTriAreaAlpha = l.bigTriAreaDense = 0x3FFFFFFF;
         const dim3 lgrid(std::min(p->rasterGrid, std::max(128u, pow2_at_least(std::min(lastLate, 1u << 20) * 16u))));
-        if (p->sceneHasAlphaTest) {
+        if (p->tables.hasAlphaTest) {
             hipLaunchKernelGGL(k_raster<true>, lgrid, dim3(64), l.tableCells * 4u, s, l);
             if (!directLate && wideOn) hipLaunchKernelGGL(k_raster_wide<true>, wgrid, dim3(64), 0, s, l);
             if (!directLate) { hipLaunchKernelGGL(k_raster_overflow<true>, dim3(129), dim3(256), 0, s, l); hipLaunchKernelGGL(k_raster_bins<true>, dim3(p->binGrid), dim3(BRMI_BIN_THREADS), 0, s, l); }

@@ -637,10 +637,10 @@ static GBufferArgs gbuffer_args_of(brmi_pass* p) {
     a.setup = p->wsPtr<ClusterSetup>(p->ws.clusterSetup); a.verts = p->wsPtr<ResolveVertex>(p->ws.resolveVerts); a.tris = p->wsPtr<ResolveTriangle>(p->ws.resolveTris);
     a.vertCapacity = p->resolveCapacity; a.triCapacity = p->resolveCapacity;
     a.matWords = p->wsPtr<MaterialWords>(p->ws.matWords);
-    a.clusterUv = p->sceneHasTextures ? p->wsPtr<ClusterUv>(p->ws.clusterUv) : nullptr;
-    a.uvs = p->sceneHasTextures ? p->wsPtr<float2>(p->ws.resolveUVs) : nullptr; a.uvSets = p->sceneUvSets;
-    a.colors = p->sceneHasVertexColors ? p->wsPtr<uint32_t>(p->ws.resolveColors) : nullptr;
-    if (p->sceneHasVertexColors) a.clusterUv = p->wsPtr<ClusterUv>(p->ws.clusterUv);
+    a.clusterUv = p->tables.hasTextures ? p->wsPtr<ClusterUv>(p->ws.clusterUv) : nullptr;
+    a.uvs = p->tables.hasTextures ? p->wsPtr<float2>(p->ws.resolveUVs) : nullptr; a.uvSets = p->tables.uvSets;
+    a.colors = p->tables.hasVertexColors ? p->wsPtr<uint32_t>(p->ws.resolveColors) : nullptr;
+    if (p->tables.hasVertexColors) a.clusterUv = p->wsPtr<ClusterUv>(p->ws.clusterUv);
     return a;
 }
 
@@ -654,10 +654,10 @@ static GBufferArgs gbuffer_args_of(brmi_pass* p) {
 // The ratio: a quarter of a triangle per pixel; half for scenes whose pixels fetch texcoords or vertex colours too (the in-place form decodes them per pixel).  No cut through the
 // scene's DAGs below the ratio can be such a frame, and whether recent frames were is a word the device stores for the host (no wait; a stale answer picks the other, equally
 // exact, form).  BRMI_TUNING=resolve_inline=0 / 1: never / always (tests run scenes both ways).  (Replaces round 4's marking pass, which only skipped whole clusters.)
-uint32_t resolve_inline_ratio(const brmi_pass* p) { return (p->sceneHasTextures || p->sceneHasVertexColors) ? 2u : 4u; }
+uint32_t resolve_inline_ratio(const brmi_pass* p) { return (p->tables.hasTextures || p->tables.hasVertexColors) ? 2u : 4u; }
 bool resolve_inline_frame(brmi_pass* p) {
     if (p->resolveInlineMode >= 0) return p->resolveInlineMode != 0;
-    return (uint64_t)p->totalBits * BRMI_MESHLET_MAX_TRIS * resolve_inline_ratio(p) > p->bandPixelCount && p->ensureFeedback() && reinterpret_cast<volatile uint32_t*>(p->phase2FeedbackHost)[1] != 0u;
+    return (uint64_t)p->tables.totalBits * BRMI_MESHLET_MAX_TRIS * resolve_inline_ratio(p) > p->bandPixelCount && p->ensureFeedback() && reinterpret_cast<volatile uint32_t*>(p->phase2FeedbackHost)[1] != 0u;
 }
 int launch_resolve_setup(brmi_pass* p, hipStream_t s, uint32_t part) {
     if (int rc = ensure_frame_constants(p, s)) return rc;
@@ -702,23 +702,23 @@ int launch_gbuffer(brmi_pass* p, hipStream_t s) {
         a.variantSelect = lean ? 0u : 1u;
         // the texture-sampling variants' waves live long: twice the workgroups shorten the tail (Sponza 4K textured 486 -> 472 us, parallax 1001 -> 963);
         // the constant-factor variant is best at 4096
-        const uint32_t grid = (p->sceneHasTextures || p->sceneHasVertexColors) ? 8192u : (p->shadeSharesChip ? p->gbufferGridShared : 4096u);
+        const uint32_t grid = (p->tables.hasTextures || p->tables.hasVertexColors) ? 8192u : (p->shadeSharesChip ? p->gbufferGridShared : 4096u);
         hipLaunchKernelGGL(leanKernel, dim3(grid), dim3(256), 0, s, a);
         if (!lean) { a.variantSelect = 2u; hipLaunchKernelGGL(fallbackKernel, dim3(4096), dim3(256), 0, s, a); }
     };
-    if (p->sceneHasTextures || p->sceneHasVertexColors) {
-        const bool multiUv = p->sceneUvSets > 1;
+    if (p->tables.hasTextures || p->tables.hasVertexColors) {
+        const bool multiUv = p->tables.uvSets > 1;
         // (SLIM: 0 / 1 / 2 as decided above)
 #define BRMI_GB_LAUNCH(T, P, M) do { if (slim == 2) launch(k_gbuffer<false, T, P, M, 2>, k_gbuffer<true, T, P, M>); else if (slim == 1) launch(k_gbuffer<false, T, P, M, 1>, k_gbuffer<true, T, P, M>); \
                                      else launch(k_gbuffer<false, T, P, M>, k_gbuffer<true, T, P, M>); } while (0)
 #define BRMI_GBA_LAUNCH(P, M) do { if (slim == 2) launch(k_gbuffer_aniso<false, P, M, 2>, k_gbuffer_aniso<true, P, M>); else if (slim == 1) launch(k_gbuffer_aniso<false, P, M, 1>, k_gbuffer_aniso<true, P, M>); \
                                    else launch(k_gbuffer_aniso<false, P, M>, k_gbuffer_aniso<true, P, M>); } while (0)
         // a bound maxAnisotropy table (brmi_set_sampler_anisotropy) selects the ANISO instantiations; without one the launches are the ones they always were
-        if (p->samplerAniso && p->sceneHasTextures) {
-            if (p->sceneHasParallax) { if (multiUv) BRMI_GBA_LAUNCH(true, true); else BRMI_GBA_LAUNCH(true, false); }
+        if (p->samplerAniso && p->tables.hasTextures) {
+            if (p->tables.hasParallax) { if (multiUv) BRMI_GBA_LAUNCH(true, true); else BRMI_GBA_LAUNCH(true, false); }
             else if (multiUv) BRMI_GBA_LAUNCH(false, true);
             else BRMI_GBA_LAUNCH(false, false);
-        } else if (p->sceneHasParallax) { if (multiUv) BRMI_GB_LAUNCH(true, true, true); else BRMI_GB_LAUNCH(true, true, false); }      // its own variants: the ray march costs the others registers they would spill
+        } else if (p->tables.hasParallax) { if (multiUv) BRMI_GB_LAUNCH(true, true, true); else BRMI_GB_LAUNCH(true, true, false); }      // its own variants: the ray march costs the others registers they would spill
         else if (multiUv) BRMI_GB_LAUNCH(true, false, true);
         else BRMI_GB_LAUNCH(true, false, false);
     } else if (p->inlineResolve && slim == 2) launch(k_gbuffer<false, false, false, false, 2>, k_gbuffer<true, false, false, false, 2>);      // (the in-place form of scenes without textures has the slim instantiations too)
