@@ -143,7 +143,8 @@ BRMI_DEV void job_light_spheres(const brmi_scene_buffers& sc, float4* lightVS, u
     const brmi_light_info* l = sc.lights + li;
     const f3 c = xyz(mul_point(f3{l->boundingSphere[0], l->boundingSphere[1], l->boundingSphere[2]}, view));
     lightVS[i] = make_float4(c.x, c.y, c.z, l->boundingSphere[3]);
-    lightMeta[i] = (l->type & 3u) | (li << 2);
+    // the clustering's `switch (light.type)` (lightCulling.hlsl:101-116) has cases 0, 1 and 2 and no default: every other type keeps the code 3 = in no cluster
+    lightMeta[i] = min(l->type, 3u) | (li << 2);
     float4* r = shadeLights + (size_t)i * 4u;
     const f3 dir{l->dirWorldSpace[0], l->dirWorldSpace[1], l->dirWorldSpace[2]};
     if (l->type == BRMI_LIGHT_DIRECTIONAL) r[0] = make_float4(-dir.x, -dir.y, -dir.z, -1.0f);     // lightToFrag; a negative range marks the type

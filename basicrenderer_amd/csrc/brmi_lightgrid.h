@@ -129,12 +129,17 @@ BRMI_DEV void lc_fill_block(const ClusterArgs& a, uint32_t vblock, uint32_t tid)
             const uint32_t j = before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
             const uint32_t pg = j / BRMI_LIGHTS_PER_PAGE, e = j % BRMI_LIGHTS_PER_PAGE;
             if (pg < valid) {
-                a.pages[base + pg].lightIndices[e] = a.lightMeta[lb + lane] >> 2;
+                const uint32_t li = a.lightMeta[lb + lane] >> 2;
+                a.pages[base + pg].lightIndices[e] = li;
                 const uint32_t pos = listBase + (pg + 1u == valid ? e : newestCount + BRMI_LIGHTS_PER_PAGE * (valid - 2u - pg) + e);
-                a.listEntries[pos] = lb + lane;
+                // The page holds the LIGHT index (lightCulling.hlsl:105), and the walk looks that word up in activeLightIndices once more
+                // (lighting.hlsli:528: `activeLightIndices[page.lightIndices[i]]`): the light shaded is the one of list position `li`, which is this
+                // position wherever the list is the identity.  A word at or beyond numLights is a read past the reference's buffer; this position then.
+                const uint32_t rec = li < lightCount ? li : lb + lane;
+                a.listEntries[pos] = rec;
                 // the light's shading record beside its list entry: k_shade stages a cluster's lights with ONE dependent load (list position
                 // -> record) instead of two (-> light index -> record); the chain is on every tile's critical path
-                const float4* src = a.shadeLights + (size_t)(lb + lane) * 4u; float4* dst = a.listRecords + (size_t)pos * 4u;
+                const float4* src = a.shadeLights + (size_t)rec * 4u; float4* dst = a.listRecords + (size_t)pos * 4u;
                 dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2]; dst[3] = src[3];
             }
         }

@@ -667,7 +667,11 @@ BRMI_DEV uint32_t shade_pixel(const ShadeArgs& a, const ShadeFrame& k, const flo
                 if (outer > -1.5f) {                                    // spot light
                     const f3 sd{lr.r3[0], lr.r3[1], lr.r3[2]};
                     const float inner = lr.r2[3];
-                    const float cc = dot3(sd, normalize3_q(-lightToFrag));
+                    // The cone's two comparisons are decisions: they take the correctly rounded direction in both instantiations (the fast one is an ulp off, which
+                    // moved pixels on the cone's edge -- visible where inner == outer, the factor stepping from 0 to 1).  Spot lights only; recomputed, not kept live.
+                    f3 coneDir = lightToFrag;
+                    if (FAST) { const f3 t = lp - posWS; const float q = dot3(t, t); float len; coneDir = normalize3_len(t, q, len); }
+                    const float cc = dot3(sd, normalize3_q(-coneDir));
                     if (!(cc > outer)) continue;
                     if (cc < inner) { const float t = satq((cc - outer) / (inner - outer)); spot = t * t * (3.0f - 2.0f * t); }
                 }
