@@ -500,7 +500,6 @@ int brmi_update(brmi_pass* p, const brmi_frame_update* u, brmi_stream stream) {
 // What a frame's first launch has to wait for when frames are in flight (brmi_execute_split, and the stage entry points that start a frame:
 // a graph that schedules the stages itself after a split frame gets the same ordering).  No-ops when nothing was recorded.
 static int wait_for_frames_in_flight(brmi_pass* p, brmi_stream stream) {
-    if (p->frameWaitsIssued) return BRMI_OK;      // brmi_execute_split has issued them for this frame: the stage entry points it calls do not repeat them
     // this pass's previous frame may still be resolving / shading on the other stream: its visibility buffer and tables are about to be rewritten
     if (p->frameDoneRecorded) BRMI_HIP(p, hipStreamWaitEvent(static_cast<hipStream_t>(stream), p->frameDone, 0));
     p->frameDoneRecorded = false;
@@ -514,22 +513,52 @@ static int wait_for_frames_in_flight(brmi_pass* p, brmi_stream stream) {
     return BRMI_OK;
 }
 
+// The stage bodies: a launcher between its stage's two timing events, with the frame's context -- brmi_execute_split's own, or the default one of a public entry point
+// (readiness check, the in-flight waits where the stage can start a frame): a stage on its own takes no shortcut and leaves none behind.
+static int stage_clear(brmi_pass* p, brmi::FrameCtx& ctx, brmi_stream stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    STAGE_BEGIN(p, BRMI_STAGE_CLEAR, s); int rc = launch_clear(p, ctx, s); STAGE_END(p, BRMI_STAGE_CLEAR, s); return rc;
+}
+static int stage_cull(brmi_pass* p, brmi::FrameCtx& ctx, uint32_t phase, brmi_stream stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream); const int st = phase == 2 ? BRMI_STAGE_CULL2 : BRMI_STAGE_CULL;
+    STAGE_BEGIN(p, st, s); int rc = launch_cull(p, ctx, phase, s); STAGE_END(p, st, s); return rc;
+}
+static int stage_raster(brmi_pass* p, brmi::FrameCtx& ctx, uint32_t phase, brmi_stream stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream); const int st = phase == 2 ? BRMI_STAGE_RASTER2 : BRMI_STAGE_RASTER;
+    STAGE_BEGIN(p, st, s); int rc = launch_raster(p, ctx, phase, s); STAGE_END(p, st, s); return rc;
+}
+// brmi_execute's chain builds: (1) LinearDepthCopyPass1 + LinearDepthDownsamplePass1 in one kernel (the chain is built straight from the visibility keys, the depth map is
+// written on the way); (2) LinearDepthDownsamplePass2 skipped on the device when phase 2 rasterised nothing, because the final depth then equals the phase-1 depth
+static int stage_hzb(brmi_pass* p, brmi::FrameCtx& ctx, brmi_stream stream, brmi::ChainBuild build) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    STAGE_BEGIN(p, BRMI_STAGE_HZB, s); int rc = launch_hzb(p, ctx, s, build); STAGE_END(p, BRMI_STAGE_HZB, s);
+    if (rc == BRMI_OK) p->hzbValid = true;
+    return rc;
+}
+static int stage_gbuffer(brmi_pass* p, brmi::FrameCtx& ctx, brmi_stream stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    STAGE_BEGIN(p, BRMI_STAGE_GBUFFER, s); int rc = launch_gbuffer(p, ctx, s); STAGE_END(p, BRMI_STAGE_GBUFFER, s); return rc;
+}
+static int stage_light_clustering(brmi_pass* p, brmi::FrameCtx& ctx, brmi_stream stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    STAGE_BEGIN(p, BRMI_STAGE_LIGHT_CLUSTER, s); int rc = launch_light_clustering(p, ctx, s); STAGE_END(p, BRMI_STAGE_LIGHT_CLUSTER, s); return rc;
+}
+static int stage_shade(brmi_pass* p, brmi::FrameCtx& ctx, brmi_stream stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    STAGE_BEGIN(p, BRMI_STAGE_SHADE, s); int rc = launch_shade(p, ctx, s); STAGE_END(p, BRMI_STAGE_SHADE, s); return rc;
+}
+
 int brmi_clear_visibility(brmi_pass* p, brmi_stream stream) {
-    CHECK_READY(p); hipStream_t s = static_cast<hipStream_t>(stream);
+    CHECK_READY(p); brmi::FrameCtx ctx;
     if (int w = wait_for_frames_in_flight(p, stream)) return w;
-    STAGE_BEGIN(p, BRMI_STAGE_CLEAR, s); int rc = launch_clear(p, s); STAGE_END(p, BRMI_STAGE_CLEAR, s); return rc;
+    return stage_clear(p, ctx, stream);
 }
 int brmi_cull(brmi_pass* p, uint32_t phase, brmi_stream stream) {
-    CHECK_READY(p); hipStream_t s = static_cast<hipStream_t>(stream);
+    CHECK_READY(p); brmi::FrameCtx ctx;
     if (phase == 1) if (int w = wait_for_frames_in_flight(p, stream)) return w;
-    const int st = phase == 2 ? BRMI_STAGE_CULL2 : BRMI_STAGE_CULL;
-    STAGE_BEGIN(p, st, s); int rc = launch_cull(p, phase, s); STAGE_END(p, st, s); return rc;
+    return stage_cull(p, ctx, phase, stream);
 }
-int brmi_raster(brmi_pass* p, uint32_t phase, brmi_stream stream) {
-    CHECK_READY(p); hipStream_t s = static_cast<hipStream_t>(stream);
-    const int st = phase == 2 ? BRMI_STAGE_RASTER2 : BRMI_STAGE_RASTER;
-    STAGE_BEGIN(p, st, s); int rc = launch_raster(p, phase, s); STAGE_END(p, st, s); return rc;
-}
+int brmi_raster(brmi_pass* p, uint32_t phase, brmi_stream stream) { CHECK_READY(p); brmi::FrameCtx ctx; return stage_raster(p, ctx, phase, stream); }
 int brmi_depth_copy(brmi_pass* p, brmi_stream stream) {
     CHECK_READY(p); hipStream_t s = static_cast<hipStream_t>(stream);
     STAGE_BEGIN(p, BRMI_STAGE_DEPTH_COPY, s); int rc = launch_depth_copy(p, s); STAGE_END(p, BRMI_STAGE_DEPTH_COPY, s); return rc;
@@ -664,19 +693,9 @@ int brmi_debug_view(brmi_pass* p, brmi_stream stream) {
     return brmi::launch_debug_view(p, static_cast<hipStream_t>(stream));
 }
 int brmi_build_hzb(brmi_pass* p, brmi_stream stream) {
-    CHECK_READY(p); hipStream_t s = static_cast<hipStream_t>(stream);
+    CHECK_READY(p); brmi::FrameCtx ctx;
     if (!p->cfg.enableOcclusionCulling) return brmi::fail(p, BRMI_ERR_STATE, "brmi_build_hzb: the pass was created without enableOcclusionCulling");
-    STAGE_BEGIN(p, BRMI_STAGE_HZB, s); int rc = launch_hzb(p, s, false, false); STAGE_END(p, BRMI_STAGE_HZB, s);
-    if (rc == BRMI_OK) p->hzbValid = true;
-    return rc;
-}
-// brmi_execute's variants: (1) LinearDepthCopyPass1 + LinearDepthDownsamplePass1 in one kernel (the chain is built straight
-// from the visibility keys, the depth map is written on the way); (2) LinearDepthDownsamplePass2 skipped on the device when
-// phase 2 rasterised nothing, because the final depth then equals the phase-1 depth the chain was just built from.
-static int build_hzb_fused(brmi_pass* p, hipStream_t s, bool fromVisibility, bool onlyIfPhase2Drew) {
-    STAGE_BEGIN(p, BRMI_STAGE_HZB, s); int rc = launch_hzb(p, s, fromVisibility, onlyIfPhase2Drew); STAGE_END(p, BRMI_STAGE_HZB, s);
-    if (rc == BRMI_OK) p->hzbValid = true;
-    return rc;
+    return stage_hzb(p, ctx, stream, brmi::ChainBuild::FromDepthMap);
 }
 int brmi_invalidate_hzb(brmi_pass* p) {
     if (!p) return BRMI_ERR_INVALID;
@@ -699,23 +718,14 @@ int brmi_set_history_source(brmi_pass* p, brmi_pass* source) {
     if (source) source->historyUsers.push_back(p);
     return BRMI_OK;
 }
-int brmi_gbuffer(brmi_pass* p, brmi_stream stream) {
-    CHECK_READY(p); hipStream_t s = static_cast<hipStream_t>(stream);
-    STAGE_BEGIN(p, BRMI_STAGE_GBUFFER, s); int rc = launch_gbuffer(p, s); STAGE_END(p, BRMI_STAGE_GBUFFER, s); return rc;
-}
-int brmi_light_clustering(brmi_pass* p, brmi_stream stream) {
-    CHECK_READY(p); hipStream_t s = static_cast<hipStream_t>(stream);
-    STAGE_BEGIN(p, BRMI_STAGE_LIGHT_CLUSTER, s); int rc = launch_light_clustering(p, s); STAGE_END(p, BRMI_STAGE_LIGHT_CLUSTER, s); return rc;
-}
+int brmi_gbuffer(brmi_pass* p, brmi_stream stream) { CHECK_READY(p); brmi::FrameCtx ctx; return stage_gbuffer(p, ctx, stream); }
+int brmi_light_clustering(brmi_pass* p, brmi_stream stream) { CHECK_READY(p); brmi::FrameCtx ctx; return stage_light_clustering(p, ctx, stream); }
 int brmi_set_shade_slabs(brmi_pass* p, uint32_t slabs, brmi_slab_fn fn, void* user) {
     if (!p) return BRMI_ERR_INVALID;
     p->shadeSlabs = (fn && slabs > 1u) ? slabs : 0u; p->shadeSlabFn = p->shadeSlabs ? fn : nullptr; p->shadeSlabUser = p->shadeSlabs ? user : nullptr;
     return BRMI_OK;
 }
-int brmi_shade(brmi_pass* p, brmi_stream stream) {
-    CHECK_READY(p); hipStream_t s = static_cast<hipStream_t>(stream);
-    STAGE_BEGIN(p, BRMI_STAGE_SHADE, s); int rc = launch_shade(p, s); STAGE_END(p, BRMI_STAGE_SHADE, s); return rc;
-}
+int brmi_shade(brmi_pass* p, brmi_stream stream) { CHECK_READY(p); brmi::FrameCtx ctx; return stage_shade(p, ctx, stream); }
 
 // The whole chain in graph order.  K6 is folded into the G-buffer kernel (one visibility read).
 int brmi_execute(brmi_pass* p, brmi_stream stream) { return brmi_execute_split(p, stream, stream); }
@@ -733,39 +743,22 @@ int brmi_execute_split(brmi_pass* p, brmi_stream stream, brmi_stream shadeStream
     if (skybox && (rc = skybox_refusal(p))) return rc;
     p->executesSinceTimes++;
     const bool split = shadeStream != stream;
-    p->splitFrame = split;
-    // whatever way this call returns, the frame's shortcuts do not outlive it: stand-alone stage calls behind a failed frame must not find `splitFrame`
-    // (which disables the wide flat traversal), `shadeSharesChip` or the issued-waits mark still set
-    struct FrameScope { brmi_pass* p; ~FrameScope() { p->splitFrame = false; p->shadeSharesChip = false; p->frameWaitsIssued = false; p->clearFrameStateWithConstants = false; p->fuseFrameClear = false; p->seedInHzbTail = false; } } frameScope{p};
-    p->resolveSetupDone = false; p->depthFinal = false;      // (a frame that failed half-way must not leave its shortcuts to the stage entry points)
-    if ((rc = wait_for_frames_in_flight(p, stream))) return rc;
-    p->frameWaitsIssued = true;
+    if ((rc = wait_for_frames_in_flight(p, stream))) return rc;      // (once for the frame: the stage bodies below have none)
     // When the phase-1 traversal is the one-launch LDS walk and the frame constants are due anyway, the frame needs no clear launch: the
     // constants kernel zeroes the culling state and the walk's launch carries the visibility clear (brmi_cull.hip, SideClear).
     const bool rides = p->constantsSerial != p->updateSerial && p->tables.minLevelWidth <= 1024u /* the one-launch walk runs (brmi_cull.hip: HIER_CAP_MAX) */ && !p->forceLevelKernels && p->scene.activeDrawCount != 0u;
-    p->lightGridDone = false;
     // A split frame (round 4): the riders move to where they fit -- the visibility clear onto k_cull_clusters' launch (brmi_cull.hip: ClearRide), the
     // light clustering onto the shading stream, which is idle until this frame's pixel pass (below, behind the same event as the early resolve setup).
     const bool sideRiders = rides && split && (p->bandPixelCount & 1ull) == 0ull;
-    if (sideRiders) {
-        p->clearFrameStateWithConstants = true; p->clearVisibilityWithClusterCull = true;
-        rc = brmi_cull(p, 1, stream);
-        p->clearFrameStateWithConstants = false;
-        if (rc == BRMI_OK && p->clearVisibilityWithClusterCull) { p->clearVisibilityWithClusterCull = false; return brmi::fail(p, BRMI_ERR_STATE, "brmi_execute: the cluster culling did not carry the visibility clear"); }
-        if (rc) { p->clearVisibilityWithClusterCull = false; return rc; }
-    } else if (rides) {
-        p->clearFrameStateWithConstants = true; p->clearVisibilityWithTraversal = true;
-        rc = brmi_cull(p, 1, stream);
-        p->clearFrameStateWithConstants = false;
-        if (rc == BRMI_OK && p->clearVisibilityWithTraversal) { p->clearVisibilityWithTraversal = false; return brmi::fail(p, BRMI_ERR_STATE, "brmi_execute: the traversal did not carry the visibility clear"); }
-        if (rc) { p->clearVisibilityWithTraversal = false; return rc; }
-    } else {
-    p->fuseFrameClear = true;
-    rc = brmi_clear_visibility(p, stream);
-    p->fuseFrameClear = false;
-    if (rc) return rc;
-    if ((rc = brmi_cull(p, 1, stream))) return rc;
-    }
+    // the frame's plan: every fused form it asks of the launchers, here and nowhere else (brmi_internal.h: FrameCtx, whose second half they answer in)
+    brmi::FrameCtx ctx;
+    ctx.twoStreams = split;
+    ctx.visibilityClear = sideRiders ? brmi::VisibilityClear::OnClusterCull : (rides ? brmi::VisibilityClear::OnTraversal : brmi::VisibilityClear::OwnLaunch);
+    ctx.constantsClearFrameState = rides; ctx.clearTakesFrameState = !rides;
+    ctx.depthIsFinal = p->cfg.enableOcclusionCulling != 0;      // (both chain builds below come before the G-buffer kernel)
+    if (!rides && (rc = stage_clear(p, ctx, stream))) return rc;
+    if ((rc = stage_cull(p, ctx, 1, stream))) return rc;
+    if (!ctx.visibilityCleared) return brmi::fail(p, BRMI_ERR_STATE, sideRiders ? "brmi_execute: the cluster culling did not carry the visibility clear" : "brmi_execute: the traversal did not carry the visibility clear");
     // The per-cluster resolve tables need the cluster list, not the keys: for the phase-1 clusters they are made NOW, on the shading stream (idle until
     // this frame's pixel pass), beside the rasteriser -- the geometry half is a chain of latency-bound launches and this one was 40 us at its end.
     // (Not on frames of more triangles than pixels, whose setup skips clusters that own no pixel and so needs the final keys; a frame that resolves
@@ -774,23 +767,20 @@ int brmi_execute_split(brmi_pass* p, brmi_stream stream, brmi_stream shadeStream
         if (!p->cullDone) BRMI_HIP(p, hipEventCreateWithFlags(&p->cullDone, hipEventDisableTiming));
         BRMI_HIP(p, hipEventRecord(p->cullDone, static_cast<hipStream_t>(stream)));
         BRMI_HIP(p, hipStreamWaitEvent(static_cast<hipStream_t>(shadeStream), p->cullDone, 0));
-        if (sideRiders) { if ((rc = brmi::launch_light_clustering(p, static_cast<hipStream_t>(shadeStream)))) return rc; p->lightGridDone = true; }
-        if ((rc = launch_resolve_setup(p, static_cast<hipStream_t>(shadeStream), 1u))) return rc;
+        if (sideRiders && (rc = brmi::launch_light_clustering(p, ctx, static_cast<hipStream_t>(shadeStream)))) return rc;
+        if ((rc = launch_resolve_setup(p, ctx, static_cast<hipStream_t>(shadeStream), 1u))) return rc;
     }
-    if ((rc = brmi_raster(p, 1, stream))) return rc;
+    if ((rc = stage_raster(p, ctx, 1, stream))) return rc;
     if (p->cfg.enableOcclusionCulling) {
         // reference graph: LinearDepthCopyPass1 -> LinearDepthDownsamplePass1 -> HierarchicalCullingPass2 -> ...RasterizeClustersPass2
-        // -> LinearDepthCopyPass2 -> LinearDepthDownsamplePass2 (CLodExtension.cpp:1920-2088)
-        p->seedInHzbTail = true;
-        rc = build_hzb_fused(p, static_cast<hipStream_t>(stream), true, false);
-        p->seedInHzbTail = false;
-        if (rc) return rc;
-        if ((rc = brmi_cull(p, 2, stream))) return rc;
-        if ((rc = brmi_raster(p, 2, stream))) return rc;
+        // -> LinearDepthCopyPass2 -> LinearDepthDownsamplePass2 (CLodExtension.cpp:1920-2088); the first build's tail seeds phase 2
+        if ((rc = stage_hzb(p, ctx, stream, brmi::ChainBuild::AfterPhase1))) return rc;
+        if ((rc = stage_cull(p, ctx, 2, stream))) return rc;
+        if ((rc = stage_raster(p, ctx, 2, stream))) return rc;
         // LinearDepthCopyPass2 + LinearDepthDownsamplePass2 straight from the final visibility keys, skipped on the device when phase 2 drew
         // nothing: the depth map and the chain are final BEFORE the G-buffer kernel (which then skips its depth store), so a pass that
         // renders the next frame on another stream (brmi_set_history_source) can start while this frame is resolved and shaded.
-        if ((rc = build_hzb_fused(p, static_cast<hipStream_t>(stream), true, true))) return rc;
+        if ((rc = stage_hzb(p, ctx, stream, brmi::ChainBuild::AfterPhase2))) return rc;
         // recorded every frame (a pass may be linked to this one later, from another stream)
         if (!p->chainReady) BRMI_HIP(p, hipEventCreateWithFlags(&p->chainReady, hipEventDisableTiming));
         BRMI_HIP(p, hipEventRecord(p->chainReady, static_cast<hipStream_t>(stream)));
@@ -799,33 +789,21 @@ int brmi_execute_split(brmi_pass* p, brmi_stream stream, brmi_stream shadeStream
     // CLodStreamingFeedbackSortPass, behind the frame's last culling phase on the geometry stream (behind the chain event: a linked pass's next frame does not wait for it)
     if (p->streaming.on && (rc = brmi_streaming_feedback(p, stream))) return rc;
     if (split) {
-        if ((rc = launch_resolve_setup(p, static_cast<hipStream_t>(stream), 2u))) return rc;
-        p->resolveSetupDone = true;
+        if ((rc = launch_resolve_setup(p, ctx, static_cast<hipStream_t>(stream), 2u))) return rc;      // (with part 1 above: the G-buffer stage finds its tables made)
         if (!p->geometryDone) BRMI_HIP(p, hipEventCreateWithFlags(&p->geometryDone, hipEventDisableTiming));
         if (!p->frameDone) BRMI_HIP(p, hipEventCreateWithFlags(&p->frameDone, hipEventDisableTiming));
         BRMI_HIP(p, hipEventRecord(p->geometryDone, static_cast<hipStream_t>(stream)));
         BRMI_HIP(p, hipStreamWaitEvent(static_cast<hipStream_t>(shadeStream), p->geometryDone, 0));
         stream = shadeStream;
     }
-    const bool lightsDone = p->lightGridDone;      // the culling pass's launches carried the light clustering
-    p->lightGridDone = false;
-    p->depthFinal = p->cfg.enableOcclusionCulling != 0;
-    p->shadeSharesChip = split;
-    rc = brmi_gbuffer(p, stream);
-    p->shadeSharesChip = false;
-    p->depthFinal = false;
-    if (rc) return rc;
-    if (!lightsDone && (rc = brmi_light_clustering(p, stream))) return rc;
-    p->shadeSharesChip = split;
-    rc = brmi_shade(p, stream);
-    p->shadeSharesChip = false;
-    if (rc) return rc;
+    if ((rc = stage_gbuffer(p, ctx, stream))) return rc;
+    if (!ctx.lightGridBuilt && (rc = stage_light_clustering(p, ctx, stream))) return rc;      // (not where the culling pass's launches, or the shading stream beside them, carried it)
+    if ((rc = stage_shade(p, ctx, stream))) return rc;
     // SkyboxRenderPass behind the deferred shading (the reference's Deferred -> Skybox -> Forward), only where the bound environment asks for it
     if (skybox && (rc = brmi_skybox(p, stream))) return rc;
     // the debug payload of perFrame.outputType, from the surfaces the frame has just made (behind the shading stage, on its stream, in front of the frame's end)
     if (debugView && (rc = brmi_debug_view(p, stream))) return rc;
     if (split) { BRMI_HIP(p, hipEventRecord(p->frameDone, static_cast<hipStream_t>(stream))); p->frameDoneRecorded = true; }
-    p->splitFrame = false;          // (the stage entry points, called on their own, are not part of a split frame)
     return BRMI_OK;
 }
 

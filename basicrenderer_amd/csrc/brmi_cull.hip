@@ -1623,8 +1623,8 @@ static inline uint32_t grid_for(uint64_t items, uint32_t block, uint32_t maxBloc
 // level-0 frontier; per-level frontier counters start from zero
 __global__ void k_seed_phase2(uint32_t* counters, uint32_t capacity) { seed_phase2(counters, capacity, threadIdx.x); }
 
-int launch_cull(brmi_pass* p, uint32_t phase, hipStream_t s) {
-    if (int rc = ensure_frame_constants(p, s)) return rc;
+int launch_cull(brmi_pass* p, FrameCtx& ctx, uint32_t phase, hipStream_t s) {
+    if (int rc = ensure_frame_constants(p, ctx, s)) return rc;
     if (phase != 1 && phase != 2) return fail(p, BRMI_ERR_INVALID, "brmi_cull: phase %u (1 or 2)", phase);
     if (phase == 2 && !p->cfg.enableOcclusionCulling) return fail(p, BRMI_ERR_STATE, "brmi_cull: phase 2 needs a pass created with enableOcclusionCulling");
     if (phase == 2 && !p->hzbValid) return fail(p, BRMI_ERR_STATE, "brmi_cull: phase 2 needs brmi_build_hzb on the phase-1 depth first");
@@ -1672,6 +1672,8 @@ int launch_cull(brmi_pass* p, uint32_t phase, hipStream_t s) {
     auto with_residency = [&](auto launch) { if (p->streaming.on) launch(stream_args_of(p)); else launch(AllResident{}); };
     const uint32_t maxBlocks = 1024;
     bool lightGridRides = false;      // this call's launches carry the light clustering (brmi_execute)
+    // who carries the visibility clear in this call: as the frame asked, unless the flat-levels traversal below hands the walk's rider to k_cull_clusters
+    VisibilityClear carrier = phase == 1 ? ctx.visibilityClear : VisibilityClear::OwnLaunch;
     bool flatLevels = false;          // phase 1 ran the level-synchronous flat traversal: nothing is left for the walk or the level kernels
     // one launch of k_cull_hierarchy for the meshes that fit its LDS frontier, the level kernels for the rest (or for everything: tests)
     const bool hierarchy = p->tables.minLevelWidth <= HIER_CAP_MAX && !p->forceLevelKernels;
@@ -1683,15 +1685,14 @@ int launch_cull(brmi_pass* p, uint32_t phase, hipStream_t s) {
     if (spillMode) a.frontier0Counter = CNT_FRONTIER0;
     const uint32_t widthAll = spillMode ? 0xFFFFFFFFu : 0u, spillAbove = spillMode ? p->tables.spillWidth : 0xFFFFFFFFu;
     if (phase == 1) {
-        if (!p->frameStateCleared) BRMI_HIP(p, hipMemsetAsync(p->counters(), 0, p->ws.frameClearBytes, s));      // counters + both survivor bitmasks
-        p->frameStateCleared = false;
+        if (!ctx.frameStateIsClear) BRMI_HIP(p, hipMemsetAsync(p->counters(), 0, p->ws.frameClearBytes, s));      // counters + both survivor bitmasks
         // (CLodStreamingBeginFramePass: the frame's touched bits and best requests start from zero)
         if (p->streaming.on) BRMI_HIP(p, hipMemsetAsync(p->streaming.b.scratch, 0, stream_scratch_layout(p->streaming.groupCount).frameBytes, s));
         // (the first ceil(draws / 8) waves of the walk take eight draws each: hierarchies of <= 8 nodes, the flat tables of build_flat_tables (brmi_scene_tables.h))
         a.packedFlat = (hierarchy && !p->tables.flatNodes.empty() && p->packedFlat) ? 1u : 0u;
         // (not beside another frame's shading half: a 1024-thread workgroup with 40 KB of LDS waits long for a CU that can take it, and the
         // dense frame in flight went 0.795 -> 0.91 ms; alone the same frame's cull stage goes 0.180 -> 0.142 ms)
-        a.wideFlat = (hierarchy && p->tables.anyWideFlat && !p->splitFrame) ? 1u : 0u;
+        a.wideFlat = (hierarchy && p->tables.anyWideFlat && !ctx.twoStreams) ? 1u : 0u;
         // Scenes of very many draws (Zorah-class): the level-synchronous flat traversal, a lane per (instance, node) task, one launch per level of the
         // deepest hierarchy (k_cull_flat_level).  Its launches carry no riders: the visibility clear moves onto k_cull_clusters (ClearRide) and the
         // light clustering is launched by the frame where it finds none done.
@@ -1699,10 +1700,10 @@ int launch_cull(brmi_pass* p, uint32_t phase, hipStream_t s) {
         // and 24 KB of LDS find few slots beside another frame's shading waves -- San-Miguel-class, 7,577 draws: 0.848 -> 0.823 ms in flight although the stage alone is 0.107 -> 0.119;
         // the dense and Bistro-class frames, with fewer draws, lose either way)
         const uint32_t draws = p->scene.activeDrawCount, minDraws = std::max(1u, p->flatLevelsMinDraws);
-        flatLevels = hierarchy && p->tables.allMeshesFlat && !p->forceLevelKernels && (draws >= minDraws || (p->splitFrame && p->tables.maxLevelWidth > 256u && draws >= std::max(1u, minDraws / 4u)));
-        if (flatLevels) {
-            if (p->clearVisibilityWithTraversal && (p->bandPixelCount & 1ull) == 0ull) { p->clearVisibilityWithTraversal = false; p->clearVisibilityWithClusterCull = true; }
-            else if (p->clearVisibilityWithTraversal) flatLevels = false;      // (an odd pixel count: the riding clear of the walk handles it)
+        flatLevels = hierarchy && p->tables.allMeshesFlat && !p->forceLevelKernels && (draws >= minDraws || (ctx.twoStreams && p->tables.maxLevelWidth > 256u && draws >= std::max(1u, minDraws / 4u)));
+        if (flatLevels && carrier == VisibilityClear::OnTraversal) {
+            if ((p->bandPixelCount & 1ull) == 0ull) carrier = VisibilityClear::OnClusterCull;
+            else flatLevels = false;      // (an odd pixel count: the riding clear of the walk handles it)
         }
         if (flatLevels) {
             with_residency([&](auto res) { hipLaunchKernelGGL((k_cull_flat_level<true, decltype(res)>), dim3(grid_for(p->scene.activeDrawCount, 256, 8192)), dim3(256), 0, s, a, 0u, (const NodeRecord*)nullptr, fb, buckets, res); });
@@ -1717,12 +1718,12 @@ int launch_cull(brmi_pass* p, uint32_t phase, hipStream_t s) {
             // to 1024 (two launches, one per class, ran one after the other: San-Miguel-class cull 178 -> 140 us with one)
             const bool wide = p->tables.maxLevelWidth > 256u;
             const uint32_t widthHi = spillMode ? widthAll : (wide ? HIER_CAP_MAX : 256u);
-            if (p->clearVisibilityWithTraversal) {
+            if (carrier == VisibilityClear::OnTraversal) {
                 SideJobs sj{reinterpret_cast<ulonglong2*>(static_cast<unsigned long long*>(p->res[BRMI_RES_VISIBILITY]) + p->bandFirstPixel), p->bandPixelCount >> 1, hgrid.x, p->clearRiderBlocks, cluster_args_of(p)};
                 const dim3 grid(hgrid.x + sj.clearBlocks + p->numLightClusters);
                 if (wide) with_residency([&](auto res) { hipLaunchKernelGGL((k_cull_hierarchy<false, 1024, BRMI_HIER_STAGE_WIDE, true, decltype(res)>), grid, dim3(64), 0, s, a, buckets, meshWidth, 0u, widthHi, spillAbove, fa, sj, res); });
                 else with_residency([&](auto res) { hipLaunchKernelGGL((k_cull_hierarchy<false, 256, 128, true, decltype(res)>), grid, dim3(64), 0, s, a, buckets, meshWidth, 0u, widthHi, spillAbove, fa, sj, res); });
-                p->clearVisibilityWithTraversal = false; lightGridRides = true;
+                ctx.visibilityCleared = true; lightGridRides = true;
             } else if (wide) with_residency([&](auto res) { hipLaunchKernelGGL((k_cull_hierarchy<false, 1024, BRMI_HIER_STAGE_WIDE, false, decltype(res)>), hgrid, dim3(64), 0, s, a, buckets, meshWidth, 0u, widthHi, spillAbove, fa, NoSide{}, res); });
             else with_residency([&](auto res) { hipLaunchKernelGGL((k_cull_hierarchy<false, 256, 128, false, decltype(res)>), hgrid, dim3(64), 0, s, a, buckets, meshWidth, 0u, widthHi, spillAbove, fa, NoSide{}, res); });
         }
@@ -1731,8 +1732,7 @@ int launch_cull(brmi_pass* p, uint32_t phase, hipStream_t s) {
         BRMI_LAUNCH_CHECK(p, "k_cull_instances");
     } else {
         // brmi_execute seeds in the tail of the depth-chain build that precedes this call (one launch less)
-        if (!p->phase2Seeded) hipLaunchKernelGGL(k_seed_phase2, dim3(1), dim3(128), 0, s, p->counters(), a.recordCapacity);
-        p->phase2Seeded = false;
+        if (!ctx.phase2IsSeeded) hipLaunchKernelGGL(k_seed_phase2, dim3(1), dim3(128), 0, s, p->counters(), a.recordCapacity);
         const NoSide none{};
         if (hierarchy && p->tables.maxLevelWidth <= 256u) with_residency([&](auto res) { hipLaunchKernelGGL((k_cull_hierarchy<true, 256, 128, false, decltype(res)>), dim3(2048), dim3(64), 0, s, a, buckets, meshWidth, 0u, 256u, spillAbove, fa, none, res); });
         else if (hierarchy) with_residency([&](auto res) { hipLaunchKernelGGL((k_cull_hierarchy<true, 1024, BRMI_HIER_STAGE_WIDE, false, decltype(res)>), dim3(2048), dim3(64), 0, s, a, buckets, meshWidth, 0u, spillMode ? widthAll : HIER_CAP_MAX, spillAbove, fa, none, res); });
@@ -1761,11 +1761,11 @@ int launch_cull(brmi_pass* p, uint32_t phase, hipStream_t s) {
     }
     if (lightGridRides) {
         with_residency([&](auto res) { hipLaunchKernelGGL((k_cull_clusters<1, decltype(res)>), dim3(smallGrid + (p->numLightClusters + 3u) / 4u), dim3(256), 0, s, a, (const BucketRecord*)buckets, temp, bitmask, blockDirty, LcRide{smallGrid, cluster_args_of(p)}, res); });
-        p->lightGridDone = true;
-    } else if (phase == 1 && p->clearVisibilityWithClusterCull) {
+        ctx.lightGridBuilt = true;
+    } else if (carrier == VisibilityClear::OnClusterCull) {
         const uint32_t clearBlocks = 2048;
         with_residency([&](auto res) { hipLaunchKernelGGL((k_cull_clusters<2, decltype(res)>), dim3(smallGrid + clearBlocks), dim3(256), 0, s, a, (const BucketRecord*)buckets, temp, bitmask, blockDirty, ClearRide{smallGrid, reinterpret_cast<ulonglong2*>(static_cast<unsigned long long*>(p->res[BRMI_RES_VISIBILITY]) + p->bandFirstPixel), p->bandPixelCount >> 1, clearBlocks}, res); });
-        p->clearVisibilityWithClusterCull = false;
+        ctx.visibilityCleared = true;
     } else with_residency([&](auto res) { hipLaunchKernelGGL((k_cull_clusters<0, decltype(res)>), dim3(smallGrid), dim3(256), 0, s, a, (const BucketRecord*)buckets, temp, bitmask, blockDirty, NoSide{}, res); });
     BRMI_LAUNCH_CHECK(p, "k_cull_clusters");
     // phase 2 appends behind the phase-1 clusters: its capacity is what phase 1 left

@@ -273,7 +273,7 @@ brmi_scene_buffers shading_scene_of(const brmi_pass* p) {
 }
 
 // Launches the constants kernel if brmi_update / brmi_set_scene happened since the last time (every stage calls this first).
-int ensure_frame_constants(brmi_pass* p, hipStream_t s) {
+int ensure_frame_constants(brmi_pass* p, FrameCtx& ctx, hipStream_t s) {
     if (p->constantsSerial == p->updateSerial) return BRMI_OK;
     if (p->pfHost.numLights > p->scene.lightCount) return fail(p, BRMI_ERR_INVALID, "perFrame.numLights (%u) exceeds the light buffer (%u)", p->pfHost.numLights, p->scene.lightCount);
     FrameJobs j;
@@ -301,7 +301,7 @@ int ensure_frame_constants(brmi_pass* p, hipStream_t s) {
     j.firstBlock[0] = 0;
     for (int k = 0; k < 6; k++) j.firstBlock[k + 1] = j.firstBlock[k] + counts[k];
     // brmi_execute without a clear launch of its own (the visibility clear rides on the traversal kernel): the frame state is zeroed here
-    j.frameState = p->wsPtr<uint4>(p->ws.counters); j.frameState16 = p->clearFrameStateWithConstants ? p->ws.frameClearBytes / 16 : 0ull;
+    j.frameState = p->wsPtr<uint4>(p->ws.counters); j.frameState16 = ctx.constantsClearFrameState ? p->ws.frameClearBytes / 16 : 0ull;
     j.firstBlock[7] = j.firstBlock[6] + (uint32_t)std::min<uint64_t>((j.frameState16 + 511u) / 512u, 4096u);
     hipLaunchKernelGGL(k_frame_constants, dim3(j.firstBlock[7] + 1u), dim3(64), 0, s, j);       // + the layer-uniformity job's block
     BRMI_LAUNCH_CHECK(p, "k_frame_constants");
@@ -319,7 +319,7 @@ int ensure_frame_constants(brmi_pass* p, hipStream_t s) {
         } else p->layerPlanesUniform = false;
         p->layerPlanesDirty = false;
     }
-    if (p->clearFrameStateWithConstants) p->frameStateCleared = true;
+    if (ctx.constantsClearFrameState) ctx.frameStateIsClear = true;
     p->constantsSerial = p->updateSerial;
     return BRMI_OK;
 }

@@ -119,7 +119,8 @@ __global__ void __launch_bounds__(1024) k_hzb_tail(HzbDesc h, uint32_t firstMip,
     hzb_tail_levels(h, firstMip, 1024u);
 }
 
-int launch_hzb(brmi_pass* p, hipStream_t s, bool fromVisibility, bool onlyIfPhase2Drew) {
+int launch_hzb(brmi_pass* p, FrameCtx& ctx, hipStream_t s, ChainBuild build) {
+    bool fromVisibility = build != ChainBuild::FromDepthMap; const bool onlyIfPhase2Drew = build == ChainBuild::AfterPhase2;
     const HzbDesc h = p->hzbDesc();
     const bool head = h.paddedW >= 32 && h.paddedH >= 32;
     if (fromVisibility && !head) { int rc = launch_depth_copy(p, s); if (rc) return rc; fromVisibility = false; }   // tiny targets: unfused
@@ -127,8 +128,7 @@ int launch_hzb(brmi_pass* p, hipStream_t s, bool fromVisibility, bool onlyIfPhas
     // Round 6: a frame whose phase-1 rasteriser stage built the chain itself (brmi_raster.hip: the re-test reads it) has the chain of everything but the late pass; the
     // build from the visibility keys that follows that stage redoes the late pass's blocks only -- nothing at all when the late list stayed empty.  (A build from the
     // depth map, brmi_build_hzb after brmi_depth_copy, redoes everything as always.)
-    const bool lateOnly = p->chainBuiltInRaster && fromVisibility && !onlyIfPhase2Drew;
-    p->chainBuiltInRaster = false;
+    const bool lateOnly = ctx.chainBuiltByRaster && fromVisibility && build == ChainBuild::AfterPhase1;
     const uint32_t* skip = onlyIfPhase2Drew ? p->counters() + CNT_VISIBLE2 : (lateOnly ? p->counters() + CNT_LATE1 : nullptr);
     uint32_t first = 1;
     if (head) {
@@ -143,15 +143,15 @@ int launch_hzb(brmi_pass* p, hipStream_t s, bool fromVisibility, bool onlyIfPhas
         }
         const dim3 grid(h.paddedW / 32, std::max(1u, row1 - row0));
         DirtyBlocks mk{nullptr, (p->cfg.width + 31u) / 32u};
-        if (fromVisibility && (onlyIfPhase2Drew || lateOnly) && p->chainDirtyTracked) mk.chainDirty = p->wsPtr<uint8_t>(p->ws.chainDirty);
+        if (fromVisibility && (onlyIfPhase2Drew || lateOnly) && ctx.chainDirtyBlocksKnown) mk.chainDirty = p->wsPtr<uint8_t>(p->ws.chainDirty);
         if (fromVisibility) hipLaunchKernelGGL(k_hzb_head<true>, grid, dim3(256), 0, s, h, static_cast<const unsigned long long*>(p->res[BRMI_RES_VISIBILITY]), static_cast<float*>(p->res[BRMI_RES_LINEAR_DEPTH]), skip, row0, mk);
         else hipLaunchKernelGGL(k_hzb_head<false>, grid, dim3(256), 0, s, h, (const unsigned long long*)nullptr, (float*)nullptr, skip, row0, mk);
         first = 6;
     }
     if (first < h.mipCount) {
-        const bool seed = p->seedInHzbTail && !onlyIfPhase2Drew;      // (seeding happens whether or not the levels are rebuilt)
+        const bool seed = build == ChainBuild::AfterPhase1;      // (seeding happens whether or not the levels are rebuilt)
         hipLaunchKernelGGL(k_hzb_tail, dim3(1), dim3(1024), 0, s, h, first, skip, seed ? p->counters() : nullptr, p->cfg.maxTraversalRecords);
-        if (seed) p->phase2Seeded = true;
+        if (seed) ctx.phase2IsSeeded = true;
     }
     BRMI_LAUNCH_CHECK(p, "k_hzb");
     return BRMI_OK;

@@ -270,6 +270,29 @@ struct Workspace {     // byte offsets into BRMI_RES_WORKSPACE
              meshletBoxes, pageBoxBase, pageRefs, drawList, heldRecords, lateList, wideQueue, wideAlpha, generalList, bigQueue, bigRuns, frameClearBytes, total;
 };
 
+// One frame being issued and nothing else.  Made by whoever starts the frame -- brmi_execute_split, which asks for the fused forms below, or a public stage entry
+// point, whose defaults ask for none -- and handed by reference to the stage launchers: nothing of it outlives the call.
+enum class VisibilityClear : uint8_t { OwnLaunch, OnTraversal, OnClusterCull };      // a launch of its own (launch_clear) / rides on the one-launch walk (SideJobs) / on k_cull_clusters (ClearRide)
+// which depth-chain build a launch_hzb call is: from the depth map (brmi_build_hzb behind brmi_depth_copy: everything); the phase-1 rasteriser stage's own, in front of its re-test;
+// brmi_execute's after phase 1 (from the keys; its tail also seeds phase 2; only the late pass's blocks where the rasteriser stage built) and after phase 2 (only if phase 2 drew)
+enum class ChainBuild : uint8_t { FromDepthMap, InRaster, AfterPhase1, AfterPhase2 };
+struct FrameCtx {
+    // requests: written by the frame's issuer alone, read-only to the launchers
+    bool twoStreams = false;                  // geometry and shading halves on two streams: this frame's launches share the chip with another frame's
+    VisibilityClear visibilityClear = VisibilityClear::OwnLaunch;
+    bool constantsClearFrameState = false;    // no clear launch: the constants kernel zeroes the culling pass's frame state (brmi_frame.hip)
+    bool clearTakesFrameState = false;        // the clear launch also zeroes it (the culling pass follows immediately)
+    bool depthIsFinal = false;                // the depth map is final before the G-buffer kernel runs (it skips its depth store)
+    // outcomes: written by a launcher, read by a later launcher or by the issuer
+    bool visibilityCleared = false;           // some launch so far carried the visibility clear
+    bool frameStateIsClear = false;           // ... and the frame state's (phase 1 of launch_cull then has no memset)
+    bool phase2IsSeeded = false;              // the chain build's tail did k_seed_phase2's work
+    bool lightGridBuilt = false;              // the light clustering ran (on the culling pass's launches, or on the shading stream beside them)
+    uint32_t resolveTableParts = 0;           // launch_resolve_setup parts done (1 | 2: the G-buffer stage has none left to do)
+    bool chainBuiltByRaster = false;          // the phase-1 rasteriser stage built the chain itself (ChainBuild::InRaster)
+    bool chainDirtyBlocksKnown = false;       // the last rasteriser pass recorded the 32 x 32 px blocks it may have touched (the chain build behind it skips the others)
+};
+
 }  // namespace brmi
 
 struct brmi_pass {
@@ -288,9 +311,16 @@ struct brmi_pass {
     uint64_t bandFirstPixel = 0, bandPixelCount = 0;   // tiled index range covering the band's tile rows
     uint32_t maxLevels = 1;
     brmi::SceneTables tables;        // everything derived from the scene's arrays (brmi_set_scene -> brmi_scene_tables.h: analyse_scene); uploaded by brmi_setup
+    // What outlives a call on purpose (everything else about a frame being issued is in brmi::FrameCtx):
+    // the answers of the most recent phase-1 culling, whose lists and counters the workspace holds.  Written by phase 1 of launch_cull alone; read by the stages
+    // behind it, in the same brmi_execute call or in stand-alone calls after it (launch_raster, launch_resolve_setup, launch_gbuffer).
+    bool holdThisFrame = false;      // it made a draw list (the rasteriser stage draws it, re-tests the held clusters and draws the late ones)
+    bool inlineResolve = false;      // the G-buffer pass derives a pixel's triangle from the cluster's own data (no per-cluster tables, no setup launch): frames of more
+                                     // triangles than pixels (resolve_inline_frame)
+    // the lean rasteriser's controller, from frame to frame: written and read by phase 1 of launch_raster alone
+    bool leanActive = false, leanLastLaunch = false; uint32_t leanRetryIn = 0;
     // Round 6, the draw list: whether this pass holds clusters back (brmi_raster.hip)
     bool holdEnabled = false;        // the pass can hold clusters back: occlusion culling on, no band / interleaved partition, boxes available (BRMI_TUNING hold_clusters=0: off)
-    bool holdThisFrame = false;      // this frame's phase 1 made a draw list (launch_cull -> launch_raster)
     uint32_t holdMinClusters = 16384; // hold only on frames whose last known visible-cluster count is at least this (BRMI_TUNING hold_min_clusters): below it the re-test, the late
                                      // pass and the chain's second look cost what the rasteriser saves (Bistro-class, 10 k clusters: +25 us; profiles/r06_experiments.md)
     uint32_t lateDirectMax = 128;    // the late pass walks every triangle directly (no records, plan, bins) while the last known late count is at most this (BRMI_TUNING late_direct_max;
@@ -309,9 +339,7 @@ struct brmi_pass {
     // clusters (0 = never), while at most leanMaxGeneralPct % of them come back for the general launch (else off for 64 frames).  BRMI_TUNING lean_min_clusters,
     // lean_max_general_pct, lean_grid.
     uint32_t leanMinClusters = 32768, leanMaxGeneralPct = 40, leanGrid = 24576, leanEmitGrid = 4096, leanWideEntries = 16, leanQueue = 1u << 20;      // leanQueue: entries of the binned-triangle queue (96 B each; lean_queue)
-    bool leanActive = false, leanLastLaunch = false; uint32_t leanRetryIn = 0;
     uint32_t wideMinTriangles = 4;   // the wide pass is launched while the last frame the host has seen queued at least this many (BRMI_TUNING wide_min_triangles)
-    bool chainBuiltInRaster = false; // this frame's phase-1 rasteriser stage built the chain itself (before its re-test): the build that follows redoes the late pass's blocks only
     std::vector<float> sliceStartHost; float sliceKey[3] = {0, 0, 0}; uint32_t sliceKeyN[2] = {0, 0};   // slice starts of the light-cluster grid and the inputs they were made from
     // Phase 2 of a frame usually draws nothing or a few dozen clusters; then its triangles all take the row re-deal with global atomics (one
     // launch instead of k_raster + plan + bins).  Which it is, the host learns from the frames before: the ranking kernel of phase 2 also stores
@@ -329,20 +357,12 @@ struct brmi_pass {
                                       // moves fast leaves phase 2 two to four hundred clusters of large near triangles, which the row re-deal walks in few lanes: path_fast raster2 0.12 -> 0.065 ms
                                       // (0.648 -> 0.625 ms per frame); the slow path (30 - 80 clusters) and the still camera keep the one-launch form (sweep: profiles/r05_experiments.md)
     static constexpr uint32_t clearRiderBlocks = 8192; // single-wave workgroups of the visibility clear that ride on the traversal launch
-    bool splitFrame = false;         // brmi_execute_split with two streams: this frame's launches share the chip with another frame's
     uint32_t shadeSlabs = 0; brmi_slab_fn shadeSlabFn = nullptr; void* shadeSlabUser = nullptr;      // brmi_set_shade_slabs
-    bool frameWaitsIssued = false;   // brmi_execute_split has issued this frame's cross-stream waits (the stage entry points it calls skip theirs)
     uint32_t flatLevelsMinDraws = 16384;   // BRMI_FLAT_LEVELS_MIN_DRAWS: scenes with at least this many draws (all hierarchies flat) take the level-synchronous flat traversal in phase 1
     uint32_t scanEpoch = 0;          // k_scan_chained (the survivor ranking as one launch): its block sums carry this launch count
     bool packedFlat = true;          // BRMI_FLAT_PACKED=0: one draw per wave of the traversal
     static constexpr uint32_t shadeGridShared = 10240; // workgroups of k_shade<0, 3>: shorter-lived than the stand-alone 8192 so that the other frame's small geometry launches find slots sooner (Bistro-class period 6144 / 8192 / 10240 / 12288: 0.547 / 0.539 / 0.530 / 0.531 ms; Sponza-class, whose geometry half is short: 0.386 / 0.398 / 0.398 / 0.397)
     static constexpr uint32_t gbufferGridShared = 4096; // workgroups of the lean k_gbuffer in a split frame
-    bool shadeSharesChip = false;    // brmi_execute_split with two streams: the shading half runs beside another frame's geometry half
-    bool lightGridDone = false;      // this frame's light clustering ran inside the culling pass's launches
-    bool clearVisibilityWithClusterCull = false;      // brmi_execute_split on two streams: the clear rides on k_cull_clusters instead (brmi_cull.hip: ClearRide)
-    bool clearFrameStateWithConstants = false, clearVisibilityWithTraversal = false;   // brmi_execute: no clear launch (brmi_frame.hip, brmi_cull.hip)
-    bool seedInHzbTail = false, phase2Seeded = false;           // brmi_execute: the tail of the phase-1 depth-chain build also seeds phase 2 (k_seed_phase2's work)
-    bool fuseFrameClear = false, frameStateCleared = false;   // brmi_execute: the visibility clear also clears the culling pass's frame state
     bool forceLevelKernels = false;  // BRMI_CULL_LEVEL_KERNELS=1: always use the per-level kernels (tests, very wide hierarchies)
     uint32_t totalWords = 0, scanBlocks = 0;      // words of the survivor bitmask (tables.totalBits) and its 2048-word scan blocks
     uint32_t numLightClusters = 0, lightPagePool = 0;
@@ -369,12 +389,7 @@ struct brmi_pass {
     std::vector<brmi_pass*> historyUsers;   // passes whose `history` is this pass (unlinked when it is destroyed)
     bool layerPlanesDirty = false;   // brmi_setup: the next constants launch is followed by k_fill_layer_planes
     bool layerPlanesUniform = false; // ... which found one coat and one fuzz word for the whole scene and filled both planes (read back once)
-    bool chainDirtyTracked = false;  // this frame's phase-2 rasteriser recorded the blocks it may have touched (the second chain build skips the others)
     int resolveInlineMode = -1;      // BRMI_TUNING=resolve_inline: -1 by the frame, 0 never, 1 always (tests run scenes both ways)
-    bool inlineResolve = false;      // this frame's G-buffer pass derives a pixel's triangle from the cluster's own data (no per-cluster tables, no setup launch): frames of more
-                                     // triangles than pixels, decided when the frame's culling starts (resolve_inline_frame)
-    bool resolveSetupDone = false;   // brmi_execute_split: the per-cluster tables were made on the geometry stream
-    bool depthFinal = false;         // brmi_execute: the depth map is final before the G-buffer kernel runs (it skips its depth store)
     const brmi_pass* chainOwner(uint32_t phase) const { return (phase == 1 && history) ? history : this; }
     brmi::HzbDesc hzbDesc() const;
     brmi::Workspace ws{};
@@ -408,22 +423,23 @@ long tuning(const char* key, long def);
 #define BRMI_LAUNCH_CHECK(p, what) do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return brmi::fail((p), BRMI_ERR_HIP, "launch %s: %s", (what), hipGetErrorString(e_)); } while (0)
 
 // stage launchers (one translation unit each)
-int ensure_frame_constants(brmi_pass* p, hipStream_t s);
+int ensure_frame_constants(brmi_pass* p, FrameCtx& ctx, hipStream_t s);
+inline int ensure_frame_constants(brmi_pass* p, hipStream_t s) { FrameCtx alone; return ensure_frame_constants(p, alone, s); }      // (the launchers outside a frame's chain: debug calls, skybox)
 brmi_scene_buffers shading_scene_of(const brmi_pass* p);      // p->scene with cameras / perFrame pointing at the pass's FrameSnapshot
 ShadeTables shade_tables_of(const brmi_pass* p);
-int launch_clear(brmi_pass* p, hipStream_t s);
-int launch_cull(brmi_pass* p, uint32_t phase, hipStream_t s);
-int launch_raster(brmi_pass* p, uint32_t phase, hipStream_t s);
+int launch_clear(brmi_pass* p, FrameCtx& ctx, hipStream_t s);
+int launch_cull(brmi_pass* p, FrameCtx& ctx, uint32_t phase, hipStream_t s);
+int launch_raster(brmi_pass* p, FrameCtx& ctx, uint32_t phase, hipStream_t s);
 int launch_depth_copy(brmi_pass* p, hipStream_t s);
-int launch_hzb(brmi_pass* p, hipStream_t s, bool fromVisibility, bool onlyIfPhase2Drew);
-int launch_gbuffer(brmi_pass* p, hipStream_t s);
-int launch_resolve_setup(brmi_pass* p, hipStream_t s, uint32_t part);
+int launch_hzb(brmi_pass* p, FrameCtx& ctx, hipStream_t s, ChainBuild build);
+int launch_gbuffer(brmi_pass* p, FrameCtx& ctx, hipStream_t s);
+int launch_resolve_setup(brmi_pass* p, FrameCtx& ctx, hipStream_t s, uint32_t part);
 uint32_t resolve_inline_ratio(const brmi_pass* p);
 bool resolve_inline_frame(brmi_pass* p);
-int launch_light_clustering(brmi_pass* p, hipStream_t s);
+int launch_light_clustering(brmi_pass* p, FrameCtx& ctx, hipStream_t s);
 int launch_expand_luts(brmi_pass* p, hipStream_t s);
 int launch_meshlet_boxes(brmi_pass* p, hipStream_t s);      // brmi_setup: the per-meshlet boxes of the draw list's tests, from the page contents
-int launch_shade(brmi_pass* p, hipStream_t s);
+int launch_shade(brmi_pass* p, FrameCtx& ctx, hipStream_t s);
 int launch_streaming_feedback(brmi_pass* p, hipStream_t s);
 bool debug_view_mode_built(uint32_t mode);                  // brmi_debugview.hip: the outputTypes with a payload kernel
 int launch_debug_view(brmi_pass* p, hipStream_t s);

@@ -186,14 +186,15 @@ ClusterArgs cluster_args_of(brmi_pass* p) {
     return a;
 }
 
-int launch_light_clustering(brmi_pass* p, hipStream_t s) {
-    if (int rc = ensure_frame_constants(p, s)) return rc;
+int launch_light_clustering(brmi_pass* p, FrameCtx& ctx, hipStream_t s) {
+    if (int rc = ensure_frame_constants(p, ctx, s)) return rc;
     ClusterArgs a = cluster_args_of(p);
     a.sc = shading_scene_of(p);      // may run on the shading stream of a split frame: the frame's own camera (FrameSnapshot), not the caller's buffer
     const uint32_t nc = p->numLightClusters;
     hipLaunchKernelGGL(k_lc_count, dim3((nc + 3) / 4), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_lc_fill, dim3((nc + 3) / 4), dim3(256), 0, s, a);
     BRMI_LAUNCH_CHECK(p, "light clustering");
+    ctx.lightGridBuilt = true;
     return BRMI_OK;
 }
 
@@ -223,24 +224,24 @@ ShadeArgs shade_args_of(brmi_pass* p) {
     return a;
 }
 
-static int launch_shade_range(brmi_pass* p, hipStream_t s, uint32_t row0, uint32_t row1, uint32_t share);
-int launch_shade(brmi_pass* p, hipStream_t s) {
-    if (int rc = ensure_frame_constants(p, s)) return rc;
+static int launch_shade_range(brmi_pass* p, bool sharesChip, hipStream_t s, uint32_t row0, uint32_t row1, uint32_t share);
+int launch_shade(brmi_pass* p, FrameCtx& ctx, hipStream_t s) {
+    if (int rc = ensure_frame_constants(p, ctx, s)) return rc;
     if (p->shadeSlabs > 1u && p->shadeSlabFn) {
         // brmi_set_shade_slabs: the band in slabs of whole 8-row tile rows, top to bottom; after each slab's launches the host hook (the composition of those rows)
         const uint32_t y0 = p->bandY0, y1 = p->bandY1, tileRows = (y1 - y0 + 7u) / 8u, n = std::min(p->shadeSlabs, std::max(1u, tileRows));
         for (uint32_t k = 0; k < n; k++) {
             const uint32_t r0 = y0 + (uint32_t)((uint64_t)tileRows * k / n) * 8u, r1 = std::min(y1, y0 + (uint32_t)((uint64_t)tileRows * (k + 1u) / n) * 8u);
             if (r1 <= r0) continue;
-            if (int rc = launch_shade_range(p, s, r0, r1, n)) return rc;
+            if (int rc = launch_shade_range(p, ctx.twoStreams, s, r0, r1, n)) return rc;
             p->shadeSlabFn(p->shadeSlabUser, r0, r1, static_cast<brmi_stream>(s));
         }
         return BRMI_OK;
     }
-    return launch_shade_range(p, s, p->bandY0, p->bandY1, 1u);
+    return launch_shade_range(p, ctx.twoStreams, s, p->bandY0, p->bandY1, 1u);
 }
-// the deferred shading of the band's rows [row0, row1) (row0 a multiple of 8 above the band's first row); share: the launch is one of that many
-static int launch_shade_range(brmi_pass* p, hipStream_t s, uint32_t row0, uint32_t row1, uint32_t share) {
+// the deferred shading of the band's rows [row0, row1) (row0 a multiple of 8 above the band's first row); share: the launch is one of that many; sharesChip: it runs beside another frame's geometry half
+static int launch_shade_range(brmi_pass* p, bool sharesChip, hipStream_t s, uint32_t row0, uint32_t row1, uint32_t share) {
     ShadeArgs a = shade_args_of(p);
     if (share > 1u) {
         const uint64_t first = a.firstPixel + (uint64_t)((row0 - p->bandY0) / 8u) * p->tilesX * 64ull;
@@ -253,7 +254,7 @@ static int launch_shade_range(brmi_pass* p, hipStream_t s, uint32_t row0, uint32
     // (Bistro 4K, two frames in flight: 0.436 -> 0.413 ms per frame; 16384: 0.425, 2048: 0.49)
     // a bound environment (brmi_set_environment) selects the k_shade_ibl instantiations; without one the launches are the ones they always were
     if (p->env.on) {
-        if (p->shadeSharesChip) hipLaunchKernelGGL((k_shade_ibl<0, BRMI_SHADE_WAVES>), dim3(std::max(256u, p->shadeGridShared / share)), dim3(256), 0, s, a);
+        if (sharesChip) hipLaunchKernelGGL((k_shade_ibl<0, BRMI_SHADE_WAVES>), dim3(std::max(256u, p->shadeGridShared / share)), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((k_shade_ibl<0, BRMI_SHADE_WAVES_ALONE>), dim3(std::max(256u, 8192u / share)), dim3(256), 0, s, a);
         if (p->tables.hasCoat) hipLaunchKernelGGL(k_shade_ibl<1>, dim3(512), dim3(256), 0, s, a);
         if (p->tables.hasFuzz) hipLaunchKernelGGL(k_shade_ibl<2>, dim3(512), dim3(256), 0, s, a);
@@ -261,7 +262,7 @@ static int launch_shade_range(brmi_pass* p, hipStream_t s, uint32_t row0, uint32
         BRMI_LAUNCH_CHECK(p, "k_shade_ibl");
         return BRMI_OK;
     }
-    if (p->shadeSharesChip) hipLaunchKernelGGL((k_shade<0, BRMI_SHADE_WAVES>), dim3(std::max(256u, p->shadeGridShared / share)), dim3(256), 0, s, a);
+    if (sharesChip) hipLaunchKernelGGL((k_shade<0, BRMI_SHADE_WAVES>), dim3(std::max(256u, p->shadeGridShared / share)), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((k_shade<0, BRMI_SHADE_WAVES_ALONE>), dim3(std::max(256u, 8192u / share)), dim3(256), 0, s, a);
     // deferred pixels by class: coat, fuzz, both -- only the variants some material of the scene can need
     if (p->tables.hasCoat) hipLaunchKernelGGL(k_shade<1>, dim3(512), dim3(256), 0, s, a);

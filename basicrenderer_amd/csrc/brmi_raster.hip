@@ -1471,19 +1471,19 @@ __global__ void __launch_bounds__(256) k_retest_held(RetestArgs a) {
     if ((threadIdx.x & 63u) == 0u && lateVT != 0ull) atomicAdd(reinterpret_cast<unsigned long long*>(&a.counters[CNT_DRAWN_VT]), lateVT);
 }
 
-int launch_clear(brmi_pass* p, hipStream_t s) {
+int launch_clear(brmi_pass* p, FrameCtx& ctx, hipStream_t s) {
     // inside brmi_execute the culling pass follows immediately: take its frame clear along (frameClearBytes is a multiple of 256)
-    uint4* frameState = p->fuseFrameClear ? p->wsPtr<uint4>(p->ws.counters) : nullptr;
+    uint4* frameState = ctx.clearTakesFrameState ? p->wsPtr<uint4>(p->ws.counters) : nullptr;
     hipLaunchKernelGGL(k_clear_vis, dim3(2048), dim3(256), 0, s, static_cast<unsigned long long*>(p->res[BRMI_RES_VISIBILITY]) + p->bandFirstPixel, p->bandPixelCount,
                        frameState, frameState ? p->ws.frameClearBytes / 16 : 0ull);
-    p->frameStateCleared = p->fuseFrameClear;
+    ctx.visibilityCleared = true; ctx.frameStateIsClear = ctx.clearTakesFrameState;
     BRMI_LAUNCH_CHECK(p, "k_clear_vis");
     return BRMI_OK;
 }
 
 static bool stripe_count_on(const brmi_pass* p) { return p->stripes.count > 1u; }
 
-int launch_raster(brmi_pass* p, uint32_t phase, hipStream_t s) {
+int launch_raster(brmi_pass* p, FrameCtx& ctx, uint32_t phase, hipStream_t s) {
     if (phase != 1 && phase != 2) return fail(p, BRMI_ERR_INVALID, "brmi_raster: phase %u (1 or 2)", phase);
     if (phase == 2 && !p->cfg.enableOcclusionCulling) return fail(p, BRMI_ERR_STATE, "brmi_raster: phase 2 needs a pass created with enableOcclusionCulling");
     RasterArgs a;
@@ -1505,7 +1505,7 @@ int launch_raster(brmi_pass* p, uint32_t phase, hipStream_t s) {
     const dim3 wgrid(std::max(64u, std::min(8192u, lastWide * 8u)));      // eight single-wave workgroups per queued triangle (WIDE_SHARES)
     // (the interleaved partition's surface rows are not the frame rows the boxes are in: there the second build redoes everything)
     a.chainDirty = (phase == 2 && p->stripes.count <= 1u) ? p->wsPtr<uint8_t>(p->ws.chainDirty) : nullptr; a.chainBlocksX = (p->cfg.width + 31u) / 32u;
-    p->chainDirtyTracked = a.chainDirty != nullptr;
+    ctx.chainDirtyBlocksKnown = a.chainDirty != nullptr;
     if (phase == 2) { a.firstCounter = CNT_VISIBLE; a.countCounter = CNT_VISIBLE2; }   // clusters [visible1, visible1 + visible2)
     a.vis = static_cast<unsigned long long*>(p->res[BRMI_RES_VISIBILITY]);
     a.visW = p->cfg.width; a.visH = p->frameHeight(); a.tilesX = p->tilesX; a.bandY0 = p->bandY0; a.bandY1 = p->bandY1;
@@ -1528,7 +1528,7 @@ int launch_raster(brmi_pass* p, uint32_t phase, hipStream_t s) {
     a.alphaMats = p->wsPtr<AlphaMaterial>(p->ws.alphaMats);
     // (k_raster_bins<true> packs the material index of a waiting pixel with its 12-bit tile cell into one word)
     if (p->tables.hasAlphaTest && p->scene.materialCount > (1u << 20)) return fail(p, BRMI_ERR_INVALID, "brmi_raster: %u materials in a scene with alpha-tested ones (at most %u)", p->scene.materialCount, 1u << 20);
-    if (p->tables.hasAlphaTest) if (int rc = ensure_frame_constants(p, s)) return rc;
+    if (p->tables.hasAlphaTest) if (int rc = ensure_frame_constants(p, ctx, s)) return rc;
     // the pool of k_raster_bins: four 512-thread workgroups per CU is what the LDS holds; phase 2 rarely has an item at all
     // Round 4: phase-2 launches are sized by what the host last saw phase 2 draw (the host-mapped word of the ranking kernel, read without a wait: a frame
     // or two old; every kernel here strides its grid or takes items by ticket, so any size gives the same keys).  Beside another frame's shading half a
@@ -1597,8 +1597,7 @@ int launch_raster(brmi_pass* p, uint32_t phase, hipStream_t s) {
     if (hold) {
         // the chain of the keys the draw list left (LinearDepthCopyPass1 + LinearDepthDownsamplePass1's work, done here; the frame's own build after this stage then only
         // redoes the blocks the late pass touched: launch_hzb)
-        p->chainBuiltInRaster = false;
-        if (int rc = launch_hzb(p, s, true, false)) return rc;
+        if (int rc = launch_hzb(p, ctx, s, ChainBuild::InRaster)) return rc;
         volatile uint32_t* fb = p->phase2FeedbackHost;      // words 5 / 6: the late and the held count of the frames before (no wait; any value gives the same keys)
         const uint32_t lastLate = fb ? fb[5] : 0u, lastHeld = fb ? fb[6] : 0xFFFFFFFFu;
         RetestArgs r;
@@ -1612,7 +1611,7 @@ int launch_raster(brmi_pass* p, uint32_t phase, hipStream_t s) {
         l.wideCounter = CNT_WIDE1B; l.wideFeedback = nullptr;
         // what the late pass draws changes the depth under it: it records the 32 x 32 px blocks its triangles may touch, like phase 2
         l.chainDirty = p->wsPtr<uint8_t>(p->ws.chainDirty); l.chainBlocksX = (p->cfg.width + 31u) / 32u;
-        p->chainDirtyTracked = l.chainDirty != nullptr; p->chainBuiltInRaster = true;
+        ctx.chainDirtyBlocksKnown = l.chainDirty != nullptr; ctx.chainBuiltByRaster = true;
         // few late clusters (a still or slowly moving camera: the prediction and the re-test ask the same question of nearly the same depth): every triangle through the
         // row re-deal with global atomics, ONE launch, as the small phase 2; many: records, plan and bins once more
         const bool directLate = lastLate <= (p->tables.hasAlphaTest ? 0u : p->lateDirectMax);

@@ -629,7 +629,7 @@ static GBufferArgs gbuffer_args_of(brmi_pass* p) {
     a.normals = static_cast<float4*>(p->res[BRMI_RES_GBUF_NORMALS]); a.albedo = static_cast<uint32_t*>(p->res[BRMI_RES_GBUF_ALBEDO]);
     a.coat = static_cast<unsigned long long*>(p->res[BRMI_RES_GBUF_COAT]); a.emissive = static_cast<unsigned long long*>(p->res[BRMI_RES_GBUF_EMISSIVE]);
     a.fuzz = static_cast<unsigned long long*>(p->res[BRMI_RES_GBUF_FUZZ]); a.metallicRoughness = static_cast<uint32_t*>(p->res[BRMI_RES_GBUF_METALLIC_ROUGHNESS]);
-    a.motion = static_cast<uint32_t*>(p->res[BRMI_RES_GBUF_MOTION_VECTORS]); a.depth = p->depthFinal ? nullptr : static_cast<float*>(p->res[BRMI_RES_LINEAR_DEPTH]);
+    a.motion = static_cast<uint32_t*>(p->res[BRMI_RES_GBUF_MOTION_VECTORS]); a.depth = static_cast<float*>(p->res[BRMI_RES_LINEAR_DEPTH]);
     a.W = p->cfg.width; a.H = p->cfg.height; a.tilesX = p->tilesX; a.bandY0 = p->bandY0; a.bandY1 = p->bandY1; a.firstPixel = p->bandFirstPixel; a.pixelCount = p->bandPixelCount;
     a.stripes = p->stripes;
     a.clusterCapacity = p->cfg.maxVisibleClusters;
@@ -659,8 +659,9 @@ bool resolve_inline_frame(brmi_pass* p) {
     if (p->resolveInlineMode >= 0) return p->resolveInlineMode != 0;
     return (uint64_t)p->tables.totalBits * BRMI_MESHLET_MAX_TRIS * resolve_inline_ratio(p) > p->bandPixelCount && p->ensureFeedback() && reinterpret_cast<volatile uint32_t*>(p->phase2FeedbackHost)[1] != 0u;
 }
-int launch_resolve_setup(brmi_pass* p, hipStream_t s, uint32_t part) {
-    if (int rc = ensure_frame_constants(p, s)) return rc;
+int launch_resolve_setup(brmi_pass* p, FrameCtx& ctx, hipStream_t s, uint32_t part) {
+    if (int rc = ensure_frame_constants(p, ctx, s)) return rc;
+    ctx.resolveTableParts |= part ? part : 3u;
     if (p->inlineResolve) return BRMI_OK;      // (the compaction marked every cluster "no tables")
     GBufferArgs a = gbuffer_args_of(p);
     a.hostFeedback = p->ensureFeedback() ? p->phase2FeedbackDev : nullptr;
@@ -669,8 +670,7 @@ int launch_resolve_setup(brmi_pass* p, hipStream_t s, uint32_t part) {
     const dim3 grid(part == 2u ? 512 : 8192);
     // a frame whose culling made a draw list (launch_cull; every caller is behind it, parts 0 and 2 behind the rasteriser stage with its re-test too): tables for the
     // clusters that are drawn -- part 2 takes the late list along with the phase-2 clusters (nothing with a still camera), part 0 finds every list final
-    // (holdThisFrame is written by phase 1 of launch_cull alone and outlives the brmi_execute call: brmi_gbuffer on its own finds the answer of the most recent
-    // phase-1 culling, which is the one whose lists and counters the workspace holds -- a frame's culling clears and refills them before anything here runs)
+    // (holdThisFrame stays on the pass: brmi_gbuffer on its own finds the answer of the most recent phase-1 culling -- a frame's culling clears and refills its lists before anything here runs)
     if (p->holdThisFrame) {
         hipLaunchKernelGGL(k_resolve_setup_listed, grid, dim3(64), 0, s, a, p->wsPtr<uint32_t>(p->ws.drawList), p->wsPtr<uint32_t>(p->ws.lateList));
         BRMI_LAUNCH_CHECK(p, "k_resolve_setup_listed");
@@ -681,14 +681,15 @@ int launch_resolve_setup(brmi_pass* p, hipStream_t s, uint32_t part) {
     return BRMI_OK;
 }
 
-int launch_gbuffer(brmi_pass* p, hipStream_t s) {
-    if (int rc = ensure_frame_constants(p, s)) return rc;
-    if (p->resolveSetupDone) p->resolveSetupDone = false;
-    else if (int rc = launch_resolve_setup(p, s, 0u)) return rc;
+int launch_gbuffer(brmi_pass* p, FrameCtx& ctx, hipStream_t s) {
+    if (int rc = ensure_frame_constants(p, ctx, s)) return rc;
+    // (brmi_execute_split on two streams has made the per-cluster tables on the geometry stream, in two parts)
+    if (ctx.resolveTableParts != 3u) if (int rc = launch_resolve_setup(p, ctx, s, 0u)) return rc;
     GBufferArgs a = gbuffer_args_of(p);
+    if (ctx.depthIsFinal) a.depth = nullptr;
     // inside brmi_execute with occlusion culling the depth map is final; with the layer planes holding the scene's one coat / fuzz word the
     // slim instantiations leave 20 B per pixel unwritten.  The fallback variant (arena overflow) writes everything: same values.
-    const int slim = p->depthFinal ? (p->layerPlanesUniform ? 2 : 1) : 0;
+    const int slim = ctx.depthIsFinal ? (p->layerPlanesUniform ? 2 : 1) : 0;
     const bool lean = (uint64_t)p->resolveCapacity >= (uint64_t)p->cfg.maxVisibleClusters * BRMI_MESHLET_MAX_TRIS;
     // `lean`: the arena holds every visible cluster even at 128 vertices / triangles each.  Otherwise whether one spilled is only
     // known on the device: both variants are launched and each leaves at once when the frame is the other one's (a ~5 us empty
@@ -702,7 +703,7 @@ int launch_gbuffer(brmi_pass* p, hipStream_t s) {
         a.variantSelect = lean ? 0u : 1u;
         // the texture-sampling variants' waves live long: twice the workgroups shorten the tail (Sponza 4K textured 486 -> 472 us, parallax 1001 -> 963);
         // the constant-factor variant is best at 4096
-        const uint32_t grid = (p->tables.hasTextures || p->tables.hasVertexColors) ? 8192u : (p->shadeSharesChip ? p->gbufferGridShared : 4096u);
+        const uint32_t grid = (p->tables.hasTextures || p->tables.hasVertexColors) ? 8192u : (ctx.twoStreams ? p->gbufferGridShared : 4096u);
         hipLaunchKernelGGL(leanKernel, dim3(grid), dim3(256), 0, s, a);
         if (!lean) { a.variantSelect = 2u; hipLaunchKernelGGL(fallbackKernel, dim3(4096), dim3(256), 0, s, a); }
     };

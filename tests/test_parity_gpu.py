@@ -1554,6 +1554,47 @@ def test_split_streams_without_occlusion_culling_match_the_serial_frame():
         r.close()
 
 
+UNFUSED_STAGES = (("clear_visibility",), ("cull", 1), ("raster", 1), ("depth_copy",), ("build_hzb",), ("cull", 2), ("raster", 2), ("depth_copy",), ("build_hzb",),
+                  ("gbuffer",), ("light_clustering",), ("shade",))      # examples/host_frame.cpp's order with occlusion culling: the reference graph's unfused passes
+
+
+@pytest.mark.parametrize("tuning", [{}, dict(hold_min_clusters=0), dict(flat_levels_min_draws=1)], ids=["default", "hold_min_clusters=0", "flat_levels_min_draws=1"])
+def test_a_pass_that_changes_route_from_frame_to_frame_renders_the_fused_frames(tuning):
+    """One pass issues its frames by a different route each time -- brmi_execute, the stage entry points in the unfused order, brmi_execute_split on a
+    second stream, the stage entry points again -- and every frame's keys, depth, normals and lit bytes, and both visible-cluster counts, are those of a
+    pass that calls brmi_execute four times: no route leaves anything behind that the next one finds.  A still camera, updated every frame as a host
+    does (the update is what lets brmi_execute fold the clears into the constants and culling launches).  hold_min_clusters=0: the draw list, the chain
+    built inside the rasteriser stage and the dirty-block rebuilds; flat_levels_min_draws=1: the level-synchronous traversal, where the riding
+    visibility clear changes its carrier inside the culling stage."""
+    import torch
+    from conftest import Scene
+    from basicrenderer_amd import capi
+    from basicrenderer_amd.renderer import VisibilityRenderer
+    sc = Scene("sponza", 640, 360, point_lights=8)
+    with _Env(**tuning):
+        a, b = (VisibilityRenderer(sc, occlusion=True, max_clusters=1 << 16) for _ in range(2))
+    shading = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    for frame in range(1, 5):
+        a.update(frame); a.execute()
+        b.update(frame)
+        if frame == 1:
+            b.execute()
+        elif frame == 3:
+            b.execute(shading_stream=shading)
+        else:
+            for stage in UNFUSED_STAGES:
+                b.stage(*stage)
+        torch.cuda.synchronize()
+        for rid in ("VISIBILITY", "LINEAR_DEPTH", "GBUF_NORMALS", "HDR_COLOR"):
+            n = a.descs[capi.RES[rid]]["bytes"]
+            assert n > 0 and torch.equal(a.res[capi.RES[rid]][:n], b.res[capi.RES[rid]][:n]), f"frame {frame}: {rid} differs from brmi_execute's"
+        ca, cb = a.counters(), b.counters()
+        assert (ca.visibleClusters, ca.visibleClustersPhase2) == (cb.visibleClusters, cb.visibleClustersPhase2), f"frame {frame}: visible clusters"
+        assert ca.visibleClusters > 0
+    a.close(); b.close()
+
+
 @pytest.mark.parametrize("occlusion", [False, True])
 def test_uniform_layer_planes_are_filled_once_and_skipped(occlusion):
     """brmi_config::keepUniformLayerPlanes = 1 (opt-in): a scene without coated / fuzzy materials stores one coat word and one fuzz word; the planes are
