@@ -131,6 +131,28 @@ class DebugViewBuffers(C.Structure):
     _fields_ = [("structSize", u32), ("reserved", u32), ("payload", vp), ("payloadBytes", u64), ("image", vp), ("imageBytes", u64)]
 
 
+class GtaoSettings(C.Structure):
+    """brmi_gtao_settings (include/brmi.h), 32 B."""
+    _fields_ = [("structSize", u32), ("qualityLevel", u32), ("denoisePasses", u32), ("radius", f32), ("maxDepthLod", u32), ("reserved", u32 * 3)]
+
+
+class GtaoPlane(C.Structure):
+    _fields_ = [("offset", u64), ("width", u32), ("height", u32)]
+
+
+class GtaoLayout(C.Structure):
+    """brmi_gtao_layout (include/brmi.h): where the planes of XeGTAO lie in the caller's scratch, 144 B."""
+    _fields_ = [("depth", GtaoPlane * 5), ("edges", GtaoPlane), ("term", GtaoPlane * 2), ("scratchBytes", u64), ("outputBytes", u64)]
+
+
+class GtaoBuffers(C.Structure):
+    """brmi_gtao_buffers (include/brmi.h): the settings and the caller-owned device memory of XeGTAO, 72 B."""
+    _fields_ = [("structSize", u32), ("reserved", u32), ("settings", GtaoSettings), ("scratch", vp), ("scratchBytes", u64), ("aoTerm", vp), ("aoTermBytes", u64)]
+
+
+GTAO_QUALITY = {"low": 0, "medium": 1, "high": 2, "ultra": 3}      # slices x steps: 1 x 2, 2 x 2, 3 x 3, 9 x 3
+
+
 class EnvironmentInfo(C.Structure):
     """brmi_environment_info (include/brmi_types.h): the reference's EnvironmentInfo, 128 B."""
     _fields_ = [("cubeMapDescriptorIndex", u32), ("prefilteredCubemapDescriptorIndex", u32), ("sphericalHarmonicsScale", f32),
@@ -273,7 +295,8 @@ BRMI_EXPORTS = ["brmi_abi_version", "brmi_default_config", "brmi_create", "brmi_
                 "brmi_streaming_scratch_bytes", "brmi_set_streaming", "brmi_streaming_feedback", "brmi_set_sampler_anisotropy", "brmi_debug_sample_grad",
                 "brmi_abi_minor", "brmi_debug_view_bytes", "brmi_set_debug_view", "brmi_debug_view",
                 "brmi_set_environment", "brmi_debug_ibl_lookup", "brmi_debug_ibl",
-                "brmi_skybox", "brmi_env_convert", "brmi_env_project_sh", "brmi_env_prefilter", "brmi_env_build_bytes", "brmi_debug_env_lookup"]
+                "brmi_skybox", "brmi_env_convert", "brmi_env_project_sh", "brmi_env_prefilter", "brmi_env_build_bytes", "brmi_debug_env_lookup",
+                "brmi_gtao_default_settings", "brmi_gtao_get_layout", "brmi_set_gtao", "brmi_gtao_prefilter", "brmi_gtao_main", "brmi_gtao_denoise"]
 
 
 def brmi_lib():
@@ -341,5 +364,12 @@ def brmi_lib():
             lib.brmi_env_build_bytes.argtypes = [u32, u32, C.POINTER(u64), C.POINTER(u64)]
             lib.brmi_env_build_bytes.restype = u64
             lib.brmi_debug_env_lookup.argtypes = [vp, u32, u32, vp, vp, vp, u32, vp]
+        if hasattr(lib, "brmi_set_gtao"):
+            lib.brmi_gtao_default_settings.argtypes = [C.POINTER(GtaoSettings)]
+            lib.brmi_gtao_default_settings.restype = None
+            lib.brmi_gtao_get_layout.argtypes = [u32, u32, C.POINTER(GtaoLayout)]
+            lib.brmi_set_gtao.argtypes = [vp, C.POINTER(GtaoBuffers)]
+            for n in ("brmi_gtao_prefilter", "brmi_gtao_main", "brmi_gtao_denoise"):
+                getattr(lib, n).argtypes = [vp, vp]
         _brmi_lib = lib
     return _brmi_lib

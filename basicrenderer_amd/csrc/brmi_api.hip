@@ -430,7 +430,7 @@ int brmi_update(brmi_pass* p, const brmi_frame_update* u, brmi_stream stream) {
     if (!p->setupDone) return fail(p, BRMI_ERR_STATE, "brmi_update: call brmi_setup first");
     if (p->env.on && u->perFrameHost->activeEnvironmentIndex >= p->env.b.environmentCount)      // (before anything of the pass changes: the frame before stays the last one)
         return fail(p, BRMI_ERR_INVALID, "brmi_update: perFrame.activeEnvironmentIndex %u, the bound environment table has %u entries", u->perFrameHost->activeEnvironmentIndex, p->env.b.environmentCount);
-    p->camHost = *u->mainCameraHost; p->pfHost = *u->perFrameHost;
+    p->camHost = *u->mainCameraHost; p->pfHost = *u->perFrameHost; p->frameIndexHost = u->frameIndex;
     const brmi_per_frame& pf = p->pfHost;
     if (pf.lightClusterGridSizeX != p->cfg.lightClusterSize[0] || pf.lightClusterGridSizeY != p->cfg.lightClusterSize[1] || pf.lightClusterGridSizeZ != p->cfg.lightClusterSize[2])
         return fail(p, BRMI_ERR_INVALID, "brmi_update: per-frame light cluster grid differs from the configured lightClusterSize");
@@ -543,9 +543,13 @@ static int stage_light_clustering(brmi_pass* p, brmi::FrameCtx& ctx, brmi_stream
     hipStream_t s = static_cast<hipStream_t>(stream);
     STAGE_BEGIN(p, BRMI_STAGE_LIGHT_CLUSTER, s); int rc = launch_light_clustering(p, ctx, s); STAGE_END(p, BRMI_STAGE_LIGHT_CLUSTER, s); return rc;
 }
-static int stage_shade(brmi_pass* p, brmi::FrameCtx& ctx, brmi_stream stream) {
+static int stage_shade(brmi_pass* p, brmi::FrameCtx& ctx, brmi_stream stream, bool withGtao = false) {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    STAGE_BEGIN(p, BRMI_STAGE_SHADE, s); int rc = launch_shade(p, ctx, s); STAGE_END(p, BRMI_STAGE_SHADE, s); return rc;
+    STAGE_BEGIN(p, BRMI_STAGE_SHADE, s);
+    int rc = BRMI_OK;
+    if (withGtao) { rc = launch_gtao_prefilter(p, s); if (!rc) rc = launch_gtao_main(p, s); if (!rc) rc = launch_gtao_denoise(p, s); }
+    if (!rc) rc = launch_shade(p, ctx, s);
+    STAGE_END(p, BRMI_STAGE_SHADE, s); return rc;
 }
 
 int brmi_clear_visibility(brmi_pass* p, brmi_stream stream) {
@@ -653,6 +657,60 @@ int brmi_debug_env_lookup(const brmi_texture_desc* cubemaps, uint32_t cubemapCou
     if (n == 0u) return BRMI_OK;
     return brmi::launch_debug_env_lookup(cubemaps, cubemapCount, cubemapIndex, directions, lods, outRGBA, n, static_cast<hipStream_t>(stream));
 }
+// ---- XeGTAO (brmi_gtao.hip): every refusal comes before the first launch
+void brmi_gtao_default_settings(brmi_gtao_settings* s) {
+    if (!s) return;
+    *s = brmi_gtao_settings{};
+    s->structSize = (uint32_t)sizeof(brmi_gtao_settings); s->qualityLevel = 2u; s->denoisePasses = 1u; s->radius = 0.5f; s->maxDepthLod = 0u;
+}
+int brmi_gtao_get_layout(uint32_t width, uint32_t height, brmi_gtao_layout* layout) {
+    if (!layout || width == 0u || height == 0u) return BRMI_ERR_INVALID;
+    brmi::gtao_layout(width, height, layout);
+    return BRMI_OK;
+}
+int brmi_set_gtao(brmi_pass* p, const brmi_gtao_buffers* b) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (!b) { p->gtao.on = false; p->gtao.b = brmi_gtao_buffers{}; return BRMI_OK; }
+    if (b->structSize != sizeof(brmi_gtao_buffers)) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_gtao: structSize %u, expected %zu", b->structSize, sizeof(brmi_gtao_buffers));
+    const brmi_gtao_settings& st = b->settings;
+    if (st.structSize != sizeof(brmi_gtao_settings)) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_gtao: settings.structSize %u, expected %zu", st.structSize, sizeof(brmi_gtao_settings));
+    // the taps of a pixel reach rows another GPU owns: no partition of the frame
+    if (p->cfg.bandY0 != 0u || (p->cfg.bandY1 != 0u && p->cfg.bandY1 < p->cfg.height) || p->bandY0 != 0u || p->bandY1 < p->cfg.height || p->cfg.dynamicBand || p->stripes.count > 1u)
+        return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_gtao: not with a row band, dynamicBand or the interleaved partition (a pixel's taps reach rows this GPU does not render)");
+    if (st.qualityLevel > 3u) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_gtao: qualityLevel %u (0..3)", st.qualityLevel);
+    if (st.denoisePasses > 3u) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_gtao: denoisePasses %u (0..3)", st.denoisePasses);
+    if (!std::isfinite(st.radius) || !(st.radius > 0.0f)) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_gtao: radius %g must be finite and > 0", (double)st.radius);
+    if (st.maxDepthLod > 4u) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_gtao: maxDepthLod %u (0..4)", st.maxDepthLod);
+    brmi_gtao_layout l; brmi::gtao_layout(p->cfg.width, p->cfg.height, &l);
+    if (!b->scratch || !b->aoTerm) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_gtao: a null buffer");
+    if ((reinterpret_cast<uintptr_t>(b->scratch) & 15u) || (reinterpret_cast<uintptr_t>(b->aoTerm) & 15u)) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_gtao: scratch and aoTerm must be 16 B aligned");
+    if (b->scratchBytes < l.scratchBytes) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_gtao: scratch holds %llu bytes, %u x %u pixels need %llu", (unsigned long long)b->scratchBytes, p->cfg.width, p->cfg.height, (unsigned long long)l.scratchBytes);
+    if (b->aoTermBytes < l.outputBytes) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_gtao: aoTerm holds %llu bytes, %u x %u pixels need %llu", (unsigned long long)b->aoTermBytes, p->cfg.width, p->cfg.height, (unsigned long long)l.outputBytes);
+    p->gtao.b = *b; p->gtao.layout = l; p->gtao.on = true;
+    return BRMI_OK;
+}
+// what keeps a GTAO stage from running (host state only: brmi_execute_split asks before the frame's first launch)
+static int gtao_refusal(brmi_pass* p, const char* what) {
+    if (!p->setupDone || !p->updated) return brmi::fail(p, BRMI_ERR_STATE, "%s: setup/update not done", what);
+    if (!p->gtao.on) return brmi::fail(p, BRMI_ERR_STATE, "%s: no GTAO buffers bound (brmi_set_gtao)", what);
+    if (p->bandY0 != 0u || p->bandY1 < p->cfg.height) return brmi::fail(p, BRMI_ERR_STATE, "%s: the pass renders a row band", what);
+    return BRMI_OK;
+}
+int brmi_gtao_prefilter(brmi_pass* p, brmi_stream stream) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (int rc = gtao_refusal(p, "brmi_gtao_prefilter")) return rc;
+    return brmi::launch_gtao_prefilter(p, static_cast<hipStream_t>(stream));
+}
+int brmi_gtao_main(brmi_pass* p, brmi_stream stream) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (int rc = gtao_refusal(p, "brmi_gtao_main")) return rc;
+    return brmi::launch_gtao_main(p, static_cast<hipStream_t>(stream));
+}
+int brmi_gtao_denoise(brmi_pass* p, brmi_stream stream) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (int rc = gtao_refusal(p, "brmi_gtao_denoise")) return rc;
+    return brmi::launch_gtao_denoise(p, static_cast<hipStream_t>(stream));
+}
 int brmi_streaming_feedback(brmi_pass* p, brmi_stream stream) {
     CHECK_READY(p);
     if (!p->streaming.on) return brmi::fail(p, BRMI_ERR_STATE, "brmi_streaming_feedback: no streaming buffers bound (brmi_set_streaming)");
@@ -741,6 +799,7 @@ int brmi_execute_split(brmi_pass* p, brmi_stream stream, brmi_stream shadeStream
     if (debugView && (rc = debug_view_refusal(p))) return rc;
     const bool skybox = p->env.on && p->env.b.skybox;      // ... and so is a skybox stage that could not run
     if (skybox && (rc = skybox_refusal(p))) return rc;
+    if (p->gtao.on && (rc = gtao_refusal(p, "brmi_execute"))) return rc;      // ... and the GTAO stages of a bound term
     p->executesSinceTimes++;
     const bool split = shadeStream != stream;
     if ((rc = wait_for_frames_in_flight(p, stream))) return rc;      // (once for the frame: the stage bodies below have none)
@@ -798,7 +857,8 @@ int brmi_execute_split(brmi_pass* p, brmi_stream stream, brmi_stream shadeStream
     }
     if ((rc = stage_gbuffer(p, ctx, stream))) return rc;
     if (!ctx.lightGridBuilt && (rc = stage_light_clustering(p, ctx, stream))) return rc;      // (not where the culling pass's launches, or the shading stream beside them, carried it)
-    if ((rc = stage_shade(p, ctx, stream))) return rc;
+    // BuildGTAOPipeline between the G-buffer and the deferred shading, on the shading stream, inside the shading stage's event pair (brmi_stage does not grow)
+    if ((rc = stage_shade(p, ctx, stream, p->gtao.on))) return rc;
     // SkyboxRenderPass behind the deferred shading (the reference's Deferred -> Skybox -> Forward), only where the bound environment asks for it
     if (skybox && (rc = brmi_skybox(p, stream))) return rc;
     // the debug payload of perFrame.outputType, from the surfaces the frame has just made (behind the shading stage, on its stream, in front of the frame's end)

@@ -13,6 +13,7 @@ constexpr unsigned long long kSentinel = 0xFFFFFFFFFFFFFFFFull;      // DEBUG_SE
 struct DebugViewArgs {
     const unsigned long long* vis; const float* depth; const float* normals; const uint32_t* albedo; const unsigned long long* emissive;
     const uint32_t* metallicRoughness; const uint32_t* motion;
+    const uint8_t* aoTerm;            // XeGTAO's final term where brmi_set_gtao bound one (mode AO packs the minimum the shading pass takes), else null
     const uint4* clusters; const ClusterSetup* setup; const uint32_t* counters; uint32_t clusterCapacity;
     const brmi_light_cluster* lightClusters; ShadeTables tables; const FrameSnapshot* snapshot;
     unsigned long long* payload;      // uint2 per pixel (x in the low word), tiled like the surfaces
@@ -76,7 +77,9 @@ __global__ void __launch_bounds__(256) k_debug_payload(DebugViewArgs a) {
                     const uint32_t al = __builtin_nontemporal_load(a.albedo + i);
                     out = pack_debug_float3(unorm8_to_f32(al), unorm8_to_f32(al >> 8), unorm8_to_f32(al >> 16));
                 } else if (MODE == BRMI_OUTPUT_AO) {
-                    const float ao = unorm8_to_f32(__builtin_nontemporal_load(a.albedo + i) >> 24);
+                    uint32_t code = __builtin_nontemporal_load(a.albedo + i) >> 24;
+                    if (a.aoTerm) code = min(code, (uint32_t)a.aoTerm[i]);      // (wave-uniform test)
+                    const float ao = unorm8_to_f32(code);
                     out = pack_debug_float3(ao, ao, ao);
                 } else if (MODE == BRMI_OUTPUT_METALLIC || MODE == BRMI_OUTPUT_ROUGHNESS) {
                     const float v = unorm8_to_f32(__builtin_nontemporal_load(a.metallicRoughness + i) >> (MODE == BRMI_OUTPUT_ROUGHNESS ? 8 : 0));
@@ -161,6 +164,7 @@ int launch_debug_view(brmi_pass* p, hipStream_t s) {
     a.normals = static_cast<const float*>(p->res[BRMI_RES_GBUF_NORMALS]); a.albedo = static_cast<const uint32_t*>(p->res[BRMI_RES_GBUF_ALBEDO]);
     a.emissive = static_cast<const unsigned long long*>(p->res[BRMI_RES_GBUF_EMISSIVE]); a.metallicRoughness = static_cast<const uint32_t*>(p->res[BRMI_RES_GBUF_METALLIC_ROUGHNESS]);
     a.motion = static_cast<const uint32_t*>(p->res[BRMI_RES_GBUF_MOTION_VECTORS]);
+    a.aoTerm = p->gtao.on ? static_cast<const uint8_t*>(p->gtao.b.aoTerm) : nullptr;
     a.clusters = static_cast<const uint4*>(p->res[BRMI_RES_VISIBLE_CLUSTERS]); a.setup = p->wsPtr<ClusterSetup>(p->ws.clusterSetup); a.counters = p->counters();
     a.clusterCapacity = p->cfg.maxVisibleClusters;
     a.lightClusters = static_cast<const brmi_light_cluster*>(p->res[BRMI_RES_LIGHT_CLUSTERS]); a.tables = shade_tables_of(p); a.snapshot = p->wsPtr<FrameSnapshot>(p->ws.frameSnapshot);

@@ -396,6 +396,8 @@ struct brmi_pass {
     struct { bool on = false; brmi_streaming_buffers b{}; uint32_t groupCount = 0, activeGroupScanCount = 0; } streaming;      // brmi_set_streaming (cleared by brmi_set_scene)
     struct { bool on = false; brmi_debug_view_buffers b{}; } debugView;      // brmi_set_debug_view
     struct { bool on = false; brmi_environment_buffers b{}; } env;      // brmi_set_environment (kept by brmi_set_scene: nothing of it depends on the scene)
+    struct { bool on = false; brmi_gtao_buffers b{}; brmi_gtao_layout layout{}; } gtao;      // brmi_set_gtao (kept by brmi_set_scene: sized by the frame alone)
+    uint32_t frameIndexHost = 0;                 // brmi_frame_update::frameIndex of the last brmi_update (the GTAO noise's temporal index)
     const uint32_t* samplerAniso = nullptr;      // brmi_set_sampler_anisotropy: device words, one per sampler of the scene (cleared by brmi_set_scene)
     brmi_camera camHost{};
     brmi_per_frame pfHost{};
@@ -450,6 +452,11 @@ int launch_debug_ibl(brmi_pass* p, const brmi_environment_buffers& env, uint32_t
                      const uint64_t* emissive, const uint64_t* fuzz, const float* viewWS, float* outDiffuse, float* outSpecular, uint32_t n, hipStream_t s);
 // brmi_skybox.hip / brmi_envbuild.hip (the entry points have checked their arguments)
 int launch_skybox(brmi_pass* p, hipStream_t s);
+// brmi_gtao.hip (the entry points have checked the binding)
+void gtao_layout(uint32_t width, uint32_t height, brmi_gtao_layout* l);
+int launch_gtao_prefilter(brmi_pass* p, hipStream_t s);
+int launch_gtao_main(brmi_pass* p, hipStream_t s);
+int launch_gtao_denoise(brmi_pass* p, hipStream_t s);
 int launch_env_convert(const brmi_texture_desc* equirect, const brmi_texture_desc* cube, uint32_t size, hipStream_t s);
 int launch_env_project_sh(const brmi_texture_desc* cubemaps, uint32_t cubemapCount, brmi_environment_info* env, uint32_t size, hipStream_t s);
 int launch_env_prefilter(const brmi_texture_desc* source, const brmi_texture_desc* prefiltered, uint32_t size, uint32_t levels, hipStream_t s);

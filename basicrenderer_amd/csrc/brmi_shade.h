@@ -179,6 +179,8 @@ struct ShadeArgs {
     // image-based lighting (brmi_set_environment), read by the k_shade_ibl instantiations alone.  envSH: the frame's environment as k_frame_constants folded it
     // (FrameSnapshot::envSH: nine RGB coefficients of irradianceSH, then the bits of its prefilteredCubemapDescriptorIndex)
     const float* envSH; const brmi_texture_desc* envCubemaps; uint32_t envCubemapCount, envSpecular;
+    // XeGTAO's final term (brmi_set_gtao), one visibility code per pixel in the surfaces' layout; read by the k_shade_ibl_ao instantiations alone
+    const uint8_t* aoTerm;
 };
 
 BRMI_DEV float half_at(unsigned long long v, int k) { return f16_bits_to_f32((uint32_t)(v >> (16 * k)) & 0xFFFFu); }
@@ -383,7 +385,7 @@ BRMI_DEV f3 light_contribution(const Luts& L, const Frag& f, const PixelCtx& c, 
 
 // =================================== image-based lighting =======================
 // evaluateIBL (IBL.hlsli:683-740) and what it calls, for one pixel whose Frag / PixelCtx are built.  The inputs are GetFragmentInfoScreenSpace's
-// (utilities.hlsli:2639-2709): diffuseAO = albedo.a (GTAO off), bentNormal = normalWS (lightFragment passes the normal twice), reflectedWS = reflect(-V, N) of
+// (utilities.hlsli:2639-2709): diffuseAO = albedo.a, or min(albedo.a, aoTexture / 255) with GTAO bound (:2663-2671; shade_pixel's GTAO), bentNormal = normalWS (lightFragment passes the normal twice), reflectedWS = reflect(-V, N) of
 // the adjusted normal, NdotV = max(MIN_N_DOT_V, N.V) of the STORED normal (f.NdotV, not the direct lights' saturate(dot(N, V)) of the adjusted one).
 // The direction of the cube lookups is correctly rounded fp32 without contraction (it picks a face and texels); the BRDF algebra holds the HDR tolerance like
 // the direct term's (hardware reciprocal, folded table rows, the per-code GGX fit).
@@ -533,7 +535,10 @@ BRMI_DEV void build_fragment(const ShadeArgs& a, const ShadeFrame& k, const floa
 // Returns, for a live lane whose class is not MODE, that class (MODE 0 defers such pixels); 0 otherwise.
 // IBL: an environment is bound (brmi_set_environment): evaluateIBL is the first addend of the pixel's lighting, before the light loop, as in lightFragment
 // (lighting.hlsli:406-438); instantiations of their own (k_shade_ibl), so that a pass without an environment runs the kernels it always ran.
-template <int MODE, int STASH = 0, bool IBL = false>      // STASH: floats of the metal lobe's inputs parked in LDS (0, 6 or 9)
+// GTAO (with IBL only: punctual lights never read the value, lighting.hlsli:212, :414): the environment term's visibility is min(albedo.a, aoTerm / 255).  Both are
+// codes decoded by one table, so the minimum of the codes is the code of the minimum.  A template parameter, not a null test on the pointer: the instantiations
+// without it are the kernels they were, register for register.
+template <int MODE, int STASH = 0, bool IBL = false, bool GTAO = false>      // STASH: floats of the metal lobe's inputs parked in LDS (0, 6 or 9)
 BRMI_DEV uint32_t shade_pixel(const ShadeArgs& a, const ShadeFrame& k, const float* sliceStart, const float* unorm8, const float4* camK, const RawPixel& raw, bool live, uint64_t tileBase, uint32_t within) {
     const Luts& L = k.L;
     const uint32_t gx = k.gx, gy = k.gy, gz = k.gz, nearSlices = k.nearSlices;
@@ -614,7 +619,9 @@ BRMI_DEV uint32_t shade_pixel(const ShadeArgs& a, const ShadeFrame& k, const flo
             TexelTables tb; tb.t = unorm8;
             const IblEnv env{a.envCubemaps, a.envCubemapCount, as_u32(kconst(a.envSH)[27]), a.envSpecular};
             f3 Fd, Fr;
-            evaluate_ibl<MODE>(L, tb, kconst(a.envSH), env, f, ctx, a.ggxQuads, (mr >> 8) & 0xFFu, unorm8[raw.al >> 24], unorm8[(mr >> 8) & 0xFFu], unorm8[(mr >> 16) & 0xFFu], Fd, Fr);
+            uint32_t aoCode = raw.al >> 24;
+            if (GTAO) aoCode = min(aoCode, (uint32_t)(a.aoTerm + tileBase)[within]);
+            evaluate_ibl<MODE>(L, tb, kconst(a.envSH), env, f, ctx, a.ggxQuads, (mr >> 8) & 0xFFu, unorm8[aoCode], unorm8[(mr >> 8) & 0xFFu], unorm8[(mr >> 16) & 0xFFu], Fd, Fr);
             environmentTerm = Fd + Fr;       // combineDiffuseAndSpecular: color += Fd + Fr, color = 0
         }
     }

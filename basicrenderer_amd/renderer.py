@@ -425,6 +425,50 @@ class VisibilityRenderer:
         words = self.torch.from_numpy(np.array([self._environment_index], dtype=np.int32)).to(self.device)
         pf.view(self.torch.int32)[capi.PER_FRAME_ACTIVE_ENVIRONMENT_WORD: capi.PER_FRAME_ACTIVE_ENVIRONMENT_WORD + 1].copy_(words)
 
+    # -- XeGTAO ambient occlusion (brmi_set_gtao) ---------------------------------------------------
+    def gtao_layout(self):
+        """capi.GtaoLayout of this pass's frame: where the depth levels, the edges and the working terms lie in the scratch."""
+        lay = capi.GtaoLayout()
+        self._check(self.lib.brmi_gtao_get_layout(capi.u32(self.W), capi.u32(self.H), C.byref(lay)), "brmi_gtao_get_layout", use_pass=False)
+        return lay
+
+    def set_gtao(self, quality="high", radius=0.5, denoise=1, max_depth_lod=0, fill=0, guard=0):
+        """Screen-space ambient occlusion from the next frame on: execute() runs the depth prefilter, the main pass and the denoiser between the G-buffer and
+        the shading stage, and the environment term takes min(albedo.a, term / 255).  quality: "low" | "medium" | "high" | "ultra" (or 0..3), None for off --
+        exactly the frames of a pass that never called this.  The scratch and the final term are this pass's own tensors (every byte `fill` to start with,
+        `guard` more bytes behind each that the library is not told about: gtao_guards_intact()); replacing or dropping them waits for the device first."""
+        torch = self.torch
+        if getattr(self, "_gtao", None) is not None:
+            torch.cuda.synchronize(self.device)
+        if quality is None:
+            self._check(self.lib.brmi_set_gtao(self._h, None), "brmi_set_gtao")
+            self._gtao = None
+            return
+        lay = self.gtao_layout()
+        b = capi.GtaoBuffers()
+        b.structSize = C.sizeof(capi.GtaoBuffers)
+        self.lib.brmi_gtao_default_settings(C.byref(b.settings))
+        b.settings.qualityLevel = capi.GTAO_QUALITY[quality.lower()] if isinstance(quality, str) else int(quality)
+        b.settings.radius, b.settings.denoisePasses, b.settings.maxDepthLod = float(radius), int(denoise), int(max_depth_lod)
+        scratch = torch.full((int(lay.scratchBytes) + int(guard),), int(fill), dtype=torch.uint8, device=self.device)
+        term = torch.full((int(lay.outputBytes) + int(guard),), int(fill), dtype=torch.uint8, device=self.device)
+        b.scratch, b.scratchBytes, b.aoTerm, b.aoTermBytes = scratch.data_ptr(), int(lay.scratchBytes), term.data_ptr(), int(lay.outputBytes)
+        self._check(self.lib.brmi_set_gtao(self._h, C.byref(b)), "brmi_set_gtao")
+        self._gtao = dict(buffers=b, scratch=scratch, term=term, layout=lay, fill=int(fill))
+
+    def gtao_guards_intact(self):
+        """True while the guard bytes behind set_gtao's scratch and final term still hold their fill."""
+        g = self._gtao
+        self.torch.cuda.synchronize(self.device)
+        return bool((g["scratch"][int(g["layout"].scratchBytes):] == g["fill"]).all()) and bool((g["term"][int(g["layout"].outputBytes):] == g["fill"]).all())
+
+    def ao_term(self):
+        """(H, W) uint8: XeGTAO's final visibility codes of the last frame (255 = unoccluded)."""
+        if getattr(self, "_gtao", None) is None:
+            raise BrmiError("ao_term: set_gtao first")
+        self.torch.cuda.synchronize(self.device)
+        return detile(self._gtao["term"][: int(self._gtao["layout"].outputBytes)].cpu().numpy(), self.W, self.H)
+
     # -- debug views (brmi_set_debug_view, perFrame.outputType) ------------------------------------
     def set_debug_view(self, mode, fill=0, check=True):
         """The debug view of the frames from the next update() on: a perFrame.outputType number or the reference's name without the OUTPUT_ prefix
@@ -514,6 +558,7 @@ class VisibilityRenderer:
             self.res = {}
             self._debug_view = None
             self._environment = None
+            self._gtao = None
             self._scene_keep = []
             self.device_arrays = {}
             if hasattr(self.scene, "device_arrays"):

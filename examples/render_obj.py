@@ -2,7 +2,7 @@
 """Render a Wavefront OBJ or a glTF 2.0 file (.gltf / .glb) through the whole path on an MI355X and write the lit frame as a PNG
 (Reinhard + sRGB).
 
-    python examples/render_obj.py model.obj|scene.glb out.png [--size 1920x1080] [--lights 32] [--features 0] [--view NAME]
+    python examples/render_obj.py model.obj|scene.glb out.png [--size 1920x1080] [--lights 32] [--features 0] [--environment sky] [--gtao] [--view NAME]
 
 --view NAME writes a debug view of the frame instead (perFrame.outputType: normal, albedo, metallic, roughness, emissive, ao, depth, meshlets,
 geometry_group, light_cluster_id, light_cluster_light_count, motion_vectors); pixels without geometry are black.
@@ -36,6 +36,8 @@ def main():
     ap.add_argument("--anisotropy", type=int, default=0, metavar="N", help="maxAnisotropy of every sampler, 1..16 (default: off, the isotropic sampler)")
     ap.add_argument("--environment", default=None, metavar="sky|FILE.hdr", help="image-based lighting from the procedural environment `sky` or from a Radiance .hdr panorama, built on the GPU (default: off, punctual lights only)")
     ap.add_argument("--skybox", action="store_true", help="show the environment behind the model (pixels without geometry)")
+    ap.add_argument("--gtao", nargs="?", const="high", default=None, metavar="QUALITY", help="screen-space ambient occlusion (XeGTAO) in the environment term: low, medium, high (default) or ultra; "
+                    "`--gtao --view ao` shows the visibility the shading takes")
     ap.add_argument("--view", default=None, metavar="NAME", help="write this debug view (e.g. meshlets) instead of the tone-mapped frame")
     a = ap.parse_args()
     from basicrenderer_amd import Scene
@@ -59,6 +61,8 @@ def main():
     elif a.environment:
         from basicrenderer_amd.environment import Environment, read_hdr
         r.set_environment(Environment.from_equirect(read_hdr(a.environment)), skybox=a.skybox)
+    if a.gtao:
+        r.set_gtao(a.gtao)
     if a.view:
         r.set_debug_view(a.view)
     r.execute(); r.execute()

@@ -150,7 +150,7 @@ typedef enum brmi_output_type {
     BRMI_OUTPUT_METALLIC = 3,
     BRMI_OUTPUT_ROUGHNESS = 4,
     BRMI_OUTPUT_EMISSIVE = 5,
-    BRMI_OUTPUT_AO = 6,                           /* albedo.a */
+    BRMI_OUTPUT_AO = 6,                           /* albedo.a; with brmi_set_gtao bound, min(albedo.a, aoTerm / 255) (deferred.hlsl:70-71) */
     BRMI_OUTPUT_DEPTH = 7,                        /* |linear depth| * 0.1 */
     BRMI_OUTPUT_MESHLETS = 10,                    /* page-local meshlet index of the pixel's visible cluster */
     BRMI_OUTPUT_LIGHT_CLUSTER_ID = 12,            /* the light cluster's depth slice (lighting.hlsli:509), at most lightClusterSize[2] */
@@ -344,6 +344,57 @@ int brmi_env_project_sh(const brmi_texture_desc* cubemaps, uint32_t cubemapCount
 int brmi_env_prefilter(const brmi_texture_desc* sourceCube, const brmi_texture_desc* prefiltered, uint32_t size, uint32_t levels, uint32_t prefilteredFormat,
                        brmi_stream stream);
 uint64_t brmi_env_build_bytes(uint32_t size, uint32_t levels, uint64_t* cubeBytes, uint64_t* prefilteredBytes);
+
+/* ---- XeGTAO ambient occlusion: the reference's BuildGTAOPipeline -- GTAOFilterPass, GTAOMainPass, GTAODenoisePass -----------------------
+ * Off by default: a pass that never calls brmi_set_gtao, or calls it with NULL, launches exactly what it launched before and writes the same bytes.  With it
+ * bound, brmi_execute / brmi_execute_split run the three stages between the G-buffer stage and the shading stage (on the shading stream, inside the shading
+ * stage's event pair), whether or not an environment is bound; the shading pass's environment term (k_shade_ibl) then takes
+ * diffuseAmbientOcclusion = min(albedo.a, aoTerm / 255) (utilities.hlsli:2663-2671) and BRMI_OUTPUT_AO packs that minimum.  Punctual lights never read it.
+ * brmi_shade on its own runs no GTAO stage: it reads the term the last brmi_gtao_denoise left.
+ * Every plane is in the surfaces' tiled 8x8 layout (brmi_resource_desc's formula) at its own size, in whole tiles.  All of it is caller-owned DEVICE memory,
+ * never part of brmi_declare's list (like the debug view's targets); brmi_set_scene does not forget the binding.
+ * qualityLevel 0..3 = Low (1 slice x 2 steps), Medium (2 x 2), High (3 x 3: what the reference dispatches, the default), Ultra (9 x 3).
+ * denoisePasses 0..3: 0 = one pass with blur beta 1e4 (the reference's "disabled"); 1 = one final pass, beta 1.2; n > 1 = n - 1 passes with beta / 5 that
+ * ping-pong between the two working terms, then the final one.
+ * maxDepthLod 0..4: the highest depth level a tap may read.  0 is the reference as written (its sampler's maxLod = 0 clamps SampleLevel), 4 is XeGTAO as its
+ * authors meant it; the prefilter writes all five levels either way.
+ * The temporal index of the noise is frameIndex % 64 of the frame's brmi_update; the constants (GTAOUpdateConstants) are made on the host from the main
+ * camera's fov and aspectRatio of that update and the frame size.
+ * brmi_set_gtao refuses with BRMI_ERR_INVALID, before anything is launched: a wrong structSize (of the buffers or the settings), a null, misaligned (16 B) or
+ * short scratch / aoTerm, qualityLevel > 3, denoisePasses > 3, a radius that is not finite or <= 0, maxDepthLod > 4, and A PASS WITH A ROW BAND, dynamicBand OR
+ * STRIPES: the taps of a pixel reach up to the effect radius in every direction, into rows another GPU owns and this one never rendered. */
+typedef struct brmi_gtao_settings {
+    uint32_t structSize;        /* sizeof(brmi_gtao_settings) */
+    uint32_t qualityLevel;      /* 0..3, default 2 */
+    uint32_t denoisePasses;     /* 0..3, default 1 */
+    float    radius;            /* view-space effect radius, default 0.5 */
+    uint32_t maxDepthLod;       /* 0..4, default 0 */
+    uint32_t reserved[3];       /* zero */
+} brmi_gtao_settings;           /* 32 B */
+typedef struct brmi_gtao_plane { uint64_t offset; uint32_t width, height; } brmi_gtao_plane;      /* byte offset into the scratch, size in pixels */
+typedef struct brmi_gtao_layout {
+    brmi_gtao_plane depth[5];   /* R32F: level m is max((size + 2^m - 1) >> m, 1) pixels */
+    brmi_gtao_plane edges;      /* R8: the packed edges of the main pass */
+    brmi_gtao_plane term[2];    /* R8: the working terms (the main pass writes [0]) */
+    uint64_t scratchBytes;      /* what brmi_gtao_buffers::scratch must hold */
+    uint64_t outputBytes;       /* what brmi_gtao_buffers::aoTerm must hold: 1 B per pixel, tiled, whole tiles */
+} brmi_gtao_layout;             /* 144 B */
+typedef struct brmi_gtao_buffers {
+    uint32_t structSize;        /* sizeof(brmi_gtao_buffers) */
+    uint32_t reserved;
+    brmi_gtao_settings settings;
+    void*    scratch;  uint64_t scratchBytes;
+    void*    aoTerm;   uint64_t aoTermBytes;      /* the final term: visibility code per pixel, 255 = unoccluded */
+} brmi_gtao_buffers;            /* 72 B */
+void brmi_gtao_default_settings(brmi_gtao_settings* settings);
+int  brmi_gtao_get_layout(uint32_t width, uint32_t height, brmi_gtao_layout* layout);      /* BRMI_ERR_INVALID: a null layout or an empty frame */
+int  brmi_set_gtao(brmi_pass* pass, const brmi_gtao_buffers* buffers_or_NULL);
+/* The stages.  BRMI_ERR_STATE before brmi_setup / brmi_update, or when nothing is bound.  prefilter: the linear-depth surface -> the five depth levels;
+ * main: levels + the normals plane -> edges and working term [0]; denoise: edges + working term -> aoTerm (through the second working term for
+ * denoisePasses > 1). */
+int  brmi_gtao_prefilter(brmi_pass* pass, brmi_stream stream);
+int  brmi_gtao_main(brmi_pass* pass, brmi_stream stream);
+int  brmi_gtao_denoise(brmi_pass* pass, brmi_stream stream);
 
 /* Debug views.  brmi_set_debug_view binds the targets (NULL unbinds and gives exactly the frames of a pass that never called it); with a target bound and
  * perFrame.outputType != 0, brmi_execute / brmi_execute_split run brmi_debug_view behind the shading stage (on the shading stream); an outputType the stage
