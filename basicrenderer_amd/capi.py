@@ -175,6 +175,12 @@ class TextureDesc(C.Structure):
     _fields_ = [("texels", vp), ("width", u32), ("height", u32), ("mipCount", u32), ("format", u32), ("mipOffset", u32 * 16), ("reserved", u32 * 2)]
 
 
+class MaterialInputs(C.Structure):
+    """brmi_material_inputs (include/brmi_scene.h)."""
+    _fields_ = [("structSize", u32), ("reserved", u32), ("materials", vp), ("materialCount", u32), ("openpbrCount", u32), ("openpbr", vp),
+                ("textures", vp), ("textureCount", u32), ("samplerCount", u32), ("samplers", vp), ("uvs1", vp)]
+
+
 TEXTURE_FORMAT_RGBA8_UNORM, TEXTURE_FORMAT_RGBA8_UNORM_SRGB, TEXTURE_FORMAT_RGBA16_FLOAT = 0, 1, 2      # BRMI_TEXTURE_FORMAT_*
 TEXTURE_MAX_MIPS = 16
 ENVIRONMENT_BUFFERS_SIZE_V1 = 40
@@ -271,6 +277,9 @@ def scene_lib():
         lib.brmi_scene_create_with_dag_builder.argtypes = [C.POINTER(SceneParams), vp, vp, vp]
         lib.brmi_scene_create_from_meshes.restype = vp
         lib.brmi_scene_create_from_meshes.argtypes = [C.POINTER(SceneParams), C.POINTER(MeshInput), u32, C.POINTER(InstanceInput), u32, C.POINTER(ViewInput), vp, vp, vp]
+        lib.brmi_scene_create_from_meshes_with_materials.restype = vp
+        lib.brmi_scene_create_from_meshes_with_materials.argtypes = [C.POINTER(SceneParams), C.POINTER(MeshInput), u32, C.POINTER(InstanceInput), u32, C.POINTER(ViewInput),
+                                                                      C.POINTER(MaterialInputs), vp, vp, vp]
         lib.brmi_lod_build.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.POINTER(Dag)]
         lib.brmi_lod_release.argtypes = [vp, C.POINTER(Dag)]
         lib.brmi_lod_release.restype = None
@@ -296,7 +305,8 @@ BRMI_EXPORTS = ["brmi_abi_version", "brmi_default_config", "brmi_create", "brmi_
                 "brmi_abi_minor", "brmi_debug_view_bytes", "brmi_set_debug_view", "brmi_debug_view",
                 "brmi_set_environment", "brmi_debug_ibl_lookup", "brmi_debug_ibl",
                 "brmi_skybox", "brmi_env_convert", "brmi_env_project_sh", "brmi_env_prefilter", "brmi_env_build_bytes", "brmi_debug_env_lookup",
-                "brmi_gtao_default_settings", "brmi_gtao_get_layout", "brmi_set_gtao", "brmi_gtao_prefilter", "brmi_gtao_main", "brmi_gtao_denoise"]
+                "brmi_gtao_default_settings", "brmi_gtao_get_layout", "brmi_set_gtao", "brmi_gtao_prefilter", "brmi_gtao_main", "brmi_gtao_denoise",
+                "brmi_texmips_bytes", "brmi_texmips_build", "brmi_texmips_build_alpha"]
 
 
 def brmi_lib():
@@ -371,5 +381,10 @@ def brmi_lib():
             lib.brmi_set_gtao.argtypes = [vp, C.POINTER(GtaoBuffers)]
             for n in ("brmi_gtao_prefilter", "brmi_gtao_main", "brmi_gtao_denoise"):
                 getattr(lib, n).argtypes = [vp, vp]
+        if hasattr(lib, "brmi_texmips_build"):
+            lib.brmi_texmips_bytes.argtypes = [u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+            lib.brmi_texmips_bytes.restype = u64
+            lib.brmi_texmips_build.argtypes = [C.POINTER(TextureDesc), vp, vp, u64, vp]
+            lib.brmi_texmips_build_alpha.argtypes = [C.POINTER(TextureDesc), vp, vp, vp, vp]
         _brmi_lib = lib
     return _brmi_lib

@@ -304,7 +304,13 @@ void brmi_destroy(brmi_pass* p) {
     delete p;
 }
 
-const char* brmi_last_error(const brmi_pass* p) { return p ? p->err.c_str() : "null pass"; }
+// the stages that need no pass (brmi_texmips_*) leave their refusal here, per calling thread; brmi_last_error(NULL) reads it
+static thread_local std::string g_stageError;
+static int stage_fail(int code, const char* fmt, ...) {
+    va_list ap; va_start(ap, fmt); brmi::vrefuse(g_stageError, code, fmt, ap); va_end(ap);
+    return code;
+}
+const char* brmi_last_error(const brmi_pass* p) { return p ? p->err.c_str() : (g_stageError.empty() ? "null pass" : g_stageError.c_str()); }
 
 // Provider resolution.  Copies the scene's arrays to the host once and hands them to analyse_scene (brmi_scene_tables.h), which
 // validates the cross references and derives brmi_pass::tables; what follows sizes the workspace from them.
@@ -656,6 +662,52 @@ int brmi_debug_env_lookup(const brmi_texture_desc* cubemaps, uint32_t cubemapCou
     if (!cubemaps || !directions || !lods || !outRGBA) return BRMI_ERR_INVALID;
     if (n == 0u) return BRMI_OK;
     return brmi::launch_debug_env_lookup(cubemaps, cubemapCount, cubemapIndex, directions, lods, outRGBA, n, static_cast<hipStream_t>(stream));
+}
+// ---- texture mip chains (brmi_texmips.hip): every refusal comes before the first launch
+static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0u; }
+static uint32_t full_mip_count(uint32_t w, uint32_t h) { uint32_t n = 0u; for (uint32_t m = std::max(w, h); m; m >>= 1) n++; return n; }
+static int texmips_refusal(const char* who, const brmi_texture_desc* t, const float* srgbToLinear) {
+    if (!t) return stage_fail(BRMI_ERR_INVALID, "%s: the descriptor is null", who);
+    if (!t->texels || !aligned4(t->texels)) return stage_fail(BRMI_ERR_INVALID, "%s: texels is null or not 4-byte aligned", who);
+    if (!srgbToLinear || !aligned4(srgbToLinear)) return stage_fail(BRMI_ERR_INVALID, "%s: the sRGB decode table is null or not 4-byte aligned", who);
+    if (t->format != BRMI_TEXTURE_FORMAT_RGBA8_UNORM && t->format != BRMI_TEXTURE_FORMAT_RGBA8_UNORM_SRGB)
+        return stage_fail(BRMI_ERR_INVALID, "%s: format %u is neither RGBA8_UNORM nor RGBA8_UNORM_SRGB", who, t->format);
+    if (t->width == 0u || t->height == 0u) return stage_fail(BRMI_ERR_INVALID, "%s: an empty image (%u x %u)", who, t->width, t->height);
+    if (t->mipCount == 0u || t->mipCount > BRMI_TEXTURE_MAX_MIPS) return stage_fail(BRMI_ERR_INVALID, "%s: mipCount %u is outside [1, %u]", who, t->mipCount, BRMI_TEXTURE_MAX_MIPS);
+    if (t->mipCount > full_mip_count(t->width, t->height))
+        return stage_fail(BRMI_ERR_INVALID, "%s: mipCount %u, a %u x %u image has %u levels", who, t->mipCount, t->width, t->height, full_mip_count(t->width, t->height));
+    for (uint32_t l = 0; l < t->mipCount; l++) {
+        const uint64_t nl = (uint64_t)std::max(1u, t->width >> l) * std::max(1u, t->height >> l);
+        if (t->mipOffset[l] + nl > 0x100000000ull) return stage_fail(BRMI_ERR_INVALID, "%s: level %u ends beyond what a 32-bit texel offset reaches", who, l);
+        for (uint32_t k = 0; k < l; k++) {
+            const uint64_t nk = (uint64_t)std::max(1u, t->width >> k) * std::max(1u, t->height >> k);
+            if (t->mipOffset[l] < t->mipOffset[k] + nk && t->mipOffset[k] < t->mipOffset[l] + nl) return stage_fail(BRMI_ERR_INVALID, "%s: levels %u and %u overlap (mipOffset %u and %u)", who, k, l, t->mipOffset[k], t->mipOffset[l]);
+        }
+    }
+    return BRMI_OK;
+}
+uint64_t brmi_texmips_bytes(uint32_t mipCount, uint64_t* scratchBytes, uint64_t* statsBytes, uint64_t* scalesBytes) {
+    const bool ok = mipCount != 0u && mipCount <= BRMI_TEXTURE_MAX_MIPS;
+    const uint64_t scratch = ok ? 4ull : 0ull, stats = ok ? 260ull * 4ull * mipCount : 0ull, scales = ok ? 4ull * mipCount : 0ull;
+    if (scratchBytes) *scratchBytes = scratch; if (statsBytes) *statsBytes = stats; if (scalesBytes) *scalesBytes = scales;
+    return scratch + stats + scales;
+}
+int brmi_texmips_build(const brmi_texture_desc* texture, const float* srgbToLinear, void* scratch, uint64_t scratchBytes, brmi_stream stream) {
+    if (int rc = texmips_refusal("brmi_texmips_build", texture, srgbToLinear)) return rc;
+    if (!scratch || !aligned4(scratch)) return stage_fail(BRMI_ERR_INVALID, "brmi_texmips_build: scratch is null or not 4-byte aligned");
+    if (scratchBytes < 4u) return stage_fail(BRMI_ERR_CAPACITY, "brmi_texmips_build: scratch holds %llu bytes, brmi_texmips_bytes asks for 4", (unsigned long long)scratchBytes);
+    if (texture->width > 4096u || texture->height > 4096u)
+        return stage_fail(BRMI_ERR_CAPACITY, "brmi_texmips_build: %u x %u is beyond the 4096 texels one job reduces (the reference's job split is not built)", texture->width, texture->height);
+    g_stageError.clear();
+    if (texture->mipCount == 1u) return BRMI_OK;
+    return brmi::launch_texmips_plain(*texture, srgbToLinear, static_cast<uint32_t*>(scratch), static_cast<hipStream_t>(stream));
+}
+int brmi_texmips_build_alpha(const brmi_texture_desc* texture, const float* srgbToLinear, uint32_t* stats, float* scales, brmi_stream stream) {
+    if (int rc = texmips_refusal("brmi_texmips_build_alpha", texture, srgbToLinear)) return rc;
+    if (!stats || !aligned4(stats) || !scales || !aligned4(scales)) return stage_fail(BRMI_ERR_INVALID, "brmi_texmips_build_alpha: stats or scales is null or not 4-byte aligned");
+    g_stageError.clear();
+    if (texture->mipCount == 1u) return BRMI_OK;
+    return brmi::launch_texmips_alpha(*texture, srgbToLinear, stats, scales, static_cast<hipStream_t>(stream));
 }
 // ---- XeGTAO (brmi_gtao.hip): every refusal comes before the first launch
 void brmi_gtao_default_settings(brmi_gtao_settings* s) {

@@ -461,6 +461,9 @@ int launch_env_convert(const brmi_texture_desc* equirect, const brmi_texture_des
 int launch_env_project_sh(const brmi_texture_desc* cubemaps, uint32_t cubemapCount, brmi_environment_info* env, uint32_t size, hipStream_t s);
 int launch_env_prefilter(const brmi_texture_desc* source, const brmi_texture_desc* prefiltered, uint32_t size, uint32_t levels, hipStream_t s);
 int launch_debug_env_lookup(const brmi_texture_desc* cubemaps, uint32_t cubemapCount, uint32_t cubemap, const float* dirs, const float* lods, float* outRGBA, uint32_t n, hipStream_t s);
+// brmi_texmips.hip (the entry points have checked the descriptor: a host copy, `texels` a device pointer)
+int launch_texmips_plain(const brmi_texture_desc& texture, const float* srgbToLinear, uint32_t* counter, hipStream_t s);
+int launch_texmips_alpha(const brmi_texture_desc& texture, const float* srgbToLinear, uint32_t* stats, float* scales, hipStream_t s);
 inline StreamArgs stream_args_of(const brmi_pass* p) {
     if (!p->streaming.on) return StreamArgs{nullptr, nullptr, nullptr, 0u, 0u};
     const StreamScratchLayout l = stream_scratch_layout(p->streaming.groupCount);

@@ -176,6 +176,7 @@ V3 evalPatch(const PatchDef& p, double u, double v) {
 
 struct MeshDef {
     const brmi_mesh_input* user = nullptr;      // the caller's mesh (brmi_scene_create_from_meshes) instead of patches
+    const float* userUvs1 = nullptr;            // its second UV set (brmi_material_inputs::uvs1), vertexCount x 2, or null
     std::vector<PatchDef> patches;
     uint32_t lodLevels = 1;      // DAG depth count (1 = flat)
     uint32_t material = 0;
@@ -205,6 +206,7 @@ struct MeshletBuild {
     std::vector<float> pos;       // 81*3
     std::vector<uint32_t> nrm;    // 81
     std::vector<float> uv;        // V*2 (meshes with a UV set only)
+    std::vector<float> uv1;       // V*2: the caller's own second UV set; empty = set k > 0 is derived from set 0 (derivedUv)
     std::vector<uint32_t> color;  // V RGBA8 (materialFeatures bit 5 only)
     std::vector<uint32_t> joints; // V*8 (skinned only)
     std::vector<float> weights;   // V*8
@@ -251,6 +253,7 @@ struct brmi_scene {
     std::vector<uint8_t> texels;
     std::vector<brmi_sampler_desc> samplerDescs;
     std::vector<float> srgbToLinear;
+    uint32_t userUvSets = 0;      // brmi_scene_create_from_meshes_with_materials: UV sets the caller's materials name (0 = the procedural rule)
     brmi_scene_stats stats{};
     std::vector<uint64_t> meshLod0Triangles;        // per mesh: triangles of its finest level
     bool failed = false;                            // a mesh could not be built (the DAG builder failed or returned an inconsistent DAG)
@@ -337,7 +340,8 @@ std::vector<uint8_t> buildPageBlob(const std::vector<const MeshletBuild*>& ms, b
                 const MeshletBuild* m = ms[mi];
                 const uint32_t V = m->vertCount();
                 std::vector<float> uv((size_t)V * 2);
-                for (uint32_t v = 0; v < V; v++) derivedUv(set, m->uv[v * 2], m->uv[v * 2 + 1], uv[v * 2], uv[v * 2 + 1]);
+                if (set == 1u && m->uv1.size() == (size_t)V * 2) uv = m->uv1;
+                else for (uint32_t v = 0; v < V; v++) derivedUv(set, m->uv[v * 2], m->uv[v * 2 + 1], uv[v * 2], uv[v * 2 + 1]);
                 float minU = FLT_MAX, minV = FLT_MAX, maxU = -FLT_MAX, maxV = -FLT_MAX;
                 for (uint32_t v = 0; v < V; v++) { minU = std::min(minU, uv[v * 2]); maxU = std::max(maxU, uv[v * 2]); minV = std::min(minV, uv[v * 2 + 1]); maxV = std::max(maxV, uv[v * 2 + 1]); }
                 if (V == 0) minU = minV = maxU = maxV = 0.0f;
@@ -630,6 +634,7 @@ uint32_t buildClusterLodDag(const brmi_scene& sc, const MeshDef& def, bool hasUv
         for (uint32_t v = 0; v < V; v++) {
             const uint32_t src = vref[k.firstVertex + v];
             if (hasUv) { m.uv[(size_t)v * 2] = uvs[(size_t)src * 2]; m.uv[(size_t)v * 2 + 1] = uvs[(size_t)src * 2 + 1]; }
+            if (hasUv && def.user && def.userUvs1) { m.uv1.push_back(def.userUvs1[(size_t)src * 2]); m.uv1.push_back(def.userUvs1[(size_t)src * 2 + 1]); }
             if (hasColor) m.color.push_back(colors[src]);
             for (int q = 0; q < 3; q++) m.pos[v * 3 + q] = pos[(size_t)src * 3 + q];
             m.nrm[v] = octEncode(V3{nrm[(size_t)src * 3], nrm[(size_t)src * 3 + 1], nrm[(size_t)src * 3 + 2]});
@@ -668,7 +673,7 @@ bool buildMesh(brmi_scene& sc, const MeshDef& defIn, uint32_t meshIndex) {
     std::vector<MeshletBuild> meshlets;
     std::vector<GroupBuild> groups;
     const bool hasUv = (sc.params.materialFeatures & 24u) != 0u, hasColor = (sc.params.materialFeatures & 32u) != 0u;
-    const uint32_t uvSets = hasUv ? ((sc.params.materialFeatures & 256u) ? 3u : 1u) : 0u;       // materialFeatures bit 8: pages carry three UV sets
+    const uint32_t uvSets = hasUv ? (sc.userUvSets ? sc.userUvSets : ((sc.params.materialFeatures & 256u) ? 3u : 1u)) : 0u;       // materialFeatures bit 8: pages carry three UV sets; the caller's materials: the sets they name
     const uint32_t levels = sc.params.lodBuilder != BRMI_LOD_BUILDER_QUADTREE ? buildClusterLodDag(sc, def, hasUv, hasColor, meshlets, groups) : buildQuadtreeDag(def, hasUv, hasColor, meshlets, groups);
     if (levels == 0) { sc.failed = true; return false; }
 
@@ -1706,8 +1711,67 @@ int brmi_scene_camera_at(const brmi_scene_params* params, double step, double pr
     return 0;
 }
 
-brmi_scene* brmi_scene_create_from_meshes(const brmi_scene_params* params, const brmi_mesh_input* meshes, uint32_t meshCount, const brmi_instance_input* instances, uint32_t instanceCount,
-                                          const brmi_view_input* view, brmi_dag_build_fn build, brmi_dag_release_fn release, void* user) {
+// the caller's materials, textures and samplers where addMaterials puts the procedural ones; false on input the tables cannot hold
+static bool addUserMaterials(brmi_scene& sc, const brmi_material_inputs& in) {
+    if (in.structSize != sizeof(brmi_material_inputs) || !in.materials || in.materialCount == 0 || (in.textureCount && !in.textures) || (in.samplerCount && !in.samplers) ||
+        (in.openpbrCount && !in.openpbr)) return false;
+    sc.srgbToLinear.resize(256);
+    for (int c = 0; c < 256; c++) { const double x = c / 255.0; sc.srgbToLinear[c] = (float)(x <= 0.04045 ? x / 12.92 : std::pow((x + 0.055) / 1.055, 2.4)); }
+    for (uint32_t t = 0; t < in.textureCount; t++) {
+        brmi_texture_desc d = in.textures[t];
+        if (!d.texels || d.width == 0 || d.height == 0 || d.width > 16384u || d.height > 16384u || d.mipCount == 0 || d.mipCount > BRMI_TEXTURE_MAX_MIPS ||
+            (d.format != BRMI_TEXTURE_FORMAT_RGBA8_UNORM && d.format != BRMI_TEXTURE_FORMAT_RGBA8_UNORM_SRGB)) return false;
+        uint32_t full = 0; for (uint32_t m = std::max(d.width, d.height); m; m >>= 1) full++;
+        if (d.mipCount > full) return false;
+        const uint8_t* level0 = d.texels;
+        d.texels = reinterpret_cast<const uint8_t*>((uintptr_t)sc.texels.size());
+        uint64_t at = 0;
+        for (uint32_t l = 0; l < d.mipCount; l++) { d.mipOffset[l] = (uint32_t)at; at += (uint64_t)std::max(1u, d.width >> l) * std::max(1u, d.height >> l); }
+        for (uint32_t l = d.mipCount; l < BRMI_TEXTURE_MAX_MIPS; l++) d.mipOffset[l] = 0;
+        if (at > 0xFFFFFFFFull) return false;
+        const size_t base = sc.texels.size();
+        sc.texels.resize(base + (size_t)at * 4, 0);                                 // the whole chain reserved; levels 1.. are for brmi_texmips_build[_alpha]
+        std::memcpy(sc.texels.data() + base, level0, (size_t)d.width * d.height * 4);
+        sc.textureDescs.push_back(d);
+    }
+    sc.samplerDescs.assign(in.samplers, in.samplers + in.samplerCount);
+    sc.materials.assign(in.materials, in.materials + in.materialCount);
+    uint32_t sets = 1;
+    for (brmi_material_info& m : sc.materials) {
+        const uint32_t named[8] = {m.baseColorUvSetIndex, m.normalUvSetIndex, m.metallicUvSetIndex, m.roughnessUvSetIndex, m.emissiveUvSetIndex, m.aoUvSetIndex, m.heightUvSetIndex, m.opacityUvSetIndex};
+        for (uint32_t k : named) if (k < 2u) sets = std::max(sets, k + 1u);
+    }
+    sc.userUvSets = sets;
+    // a slot a material's flags switch on must name a texture and a sampler of the tables (the kernels read a dangling index as "not bound": here it is a mistake of the caller's)
+    for (const brmi_material_info& m : sc.materials) {
+        const struct { uint32_t flag, texture, sampler; } slots[8] = {
+            {BRMI_MATERIAL_BASE_COLOR_TEXTURE, m.baseColorTextureIndex, m.baseColorSamplerIndex}, {BRMI_MATERIAL_NORMAL_MAP, m.normalTextureIndex, m.normalSamplerIndex},
+            {BRMI_MATERIAL_METALLIC_TEXTURE, m.metallicTextureIndex, m.metallicSamplerIndex}, {BRMI_MATERIAL_ROUGHNESS_TEXTURE, m.roughnessTextureIndex, m.roughnessSamplerIndex},
+            {BRMI_MATERIAL_EMISSIVE_TEXTURE, m.emissiveTextureIndex, m.emissiveSamplerIndex}, {BRMI_MATERIAL_AO_TEXTURE, m.aoMapIndex, m.aoSamplerIndex},
+            {BRMI_MATERIAL_PARALLAX, m.heightMapIndex, m.heightSamplerIndex}, {BRMI_MATERIAL_OPACITY_TEXTURE, m.opacityTextureIndex, m.opacitySamplerIndex}};
+        for (const auto& sl : slots) if ((m.materialFlags & sl.flag) && (sl.texture >= in.textureCount || sl.sampler >= in.samplerCount)) return false;
+    }
+    if (in.openpbrCount) sc.openpbr.assign(in.openpbr, in.openpbr + in.openpbrCount);
+    else for (uint32_t i = 0; i < in.materialCount; i++) {      // the base layer of the material's own factors, no coat, no fuzz
+        brmi_material_info& m = sc.materials[i];
+        m.openPBRMaterialDataIndex = i;
+        brmi_openpbr_material_info o{};
+        std::memset(&o, 0, sizeof(o));
+        o.baseWeight = 1.0f; o.baseColor[0] = m.baseColorFactor[0]; o.baseColor[1] = m.baseColorFactor[1]; o.baseColor[2] = m.baseColorFactor[2];
+        o.baseMetalness = m.metallicFactor; o.specularWeight = 1.0f; o.specularColor[0] = o.specularColor[1] = o.specularColor[2] = 1.0f;
+        o.specularRoughness = m.roughnessFactor; o.specularIor = 1.5f; o.specularAnisotropyRotationCosSin[0] = 1.0f;
+        o.coatColor[0] = o.coatColor[1] = o.coatColor[2] = 1.0f; o.coatIor = 1.6f; o.coatDarkening = 1.0f; o.coatAnisotropyRotationCosSin[0] = 1.0f;
+        o.fuzzColor[0] = o.fuzzColor[1] = o.fuzzColor[2] = 1.0f; o.fuzzRoughness = 0.5f;
+        o.transmissionColor[0] = o.transmissionColor[1] = o.transmissionColor[2] = 1.0f; o.thinFilmIor = 1.4f; o.geometryOpacity = 1.0f;
+        for (int k = 0; k < 12; k++) o.textureBindings[k] = 0xFFFFFFFFu;
+        for (int k = 0; k < 4; k++) { o.textureBindings[12 + k] = (uint32_t)k; o.textureBindings[19 + k] = (uint32_t)k; }
+        sc.openpbr.push_back(o);
+    }
+    for (const brmi_material_info& m : sc.materials) if (m.openPBRMaterialDataIndex >= sc.openpbr.size()) return false;
+    return true;
+}
+static brmi_scene* createFromMeshes(const brmi_scene_params* params, const brmi_mesh_input* meshes, uint32_t meshCount, const brmi_instance_input* instances, uint32_t instanceCount,
+                                    const brmi_view_input* view, const brmi_material_inputs* mats, brmi_dag_build_fn build, brmi_dag_release_fn release, void* user) {
     if (!params || params->width == 0 || params->height == 0 || !meshes || meshCount == 0 || !instances || instanceCount == 0 || !view) return nullptr;
     if (!(view->zNear > 0.0f) || !(view->zFar > view->zNear) || !(view->fovYDegrees > 0.0f) || !(view->fovYDegrees < 180.0f)) return nullptr;
     uint32_t materialCount = 1;
@@ -1730,9 +1794,15 @@ brmi_scene* brmi_scene_create_from_meshes(const brmi_scene_params* params, const
     else { sc->params.lodBuilder = BRMI_LOD_BUILDER_OWN; sc->dagBuild = brmi_lod_build; sc->dagRelease = brmi_lod_release; }      // (the quadtree builder only knows the procedural patches)
     for (int k = 0; k < 3; k++) { sc->stats.sceneMin[k] = 1e30f; sc->stats.sceneMax[k] = -1e30f; }
     Pcg32 rng(0xB451C0DEull + params->seed, 54u + 77u);
-    addMaterials(*sc, rng, materialCount);
+    if (!mats) addMaterials(*sc, rng, materialCount);
+    else {
+        // a mesh may only name a material of the caller's table; the pages carry a UV stream whenever a texture is there to be sampled
+        if (materialCount > mats->materialCount || !addUserMaterials(*sc, *mats)) { delete sc; return nullptr; }
+        sc->params.materialFeatures = (sc->params.materialFeatures & 32u) | (mats->textureCount ? 8u : 0u);
+    }
     for (uint32_t m = 0; m < meshCount && !sc->failed; m++) {
         MeshDef def; def.user = &meshes[m]; def.material = meshes[m].material; def.lodLevels = sc->params.lodLevels ? sc->params.lodLevels : 1;
+        if (mats && mats->uvs1) def.userUvs1 = mats->uvs1[m];
         buildMesh(*sc, def, m);
     }
     if (sc->failed) { delete sc; return nullptr; }
@@ -1751,6 +1821,16 @@ brmi_scene* brmi_scene_create_from_meshes(const brmi_scene_params* params, const
     buildLuts(*sc);
     finishFrame(*sc);
     return sc;
+}
+brmi_scene* brmi_scene_create_from_meshes(const brmi_scene_params* params, const brmi_mesh_input* meshes, uint32_t meshCount, const brmi_instance_input* instances, uint32_t instanceCount,
+                                          const brmi_view_input* view, brmi_dag_build_fn build, brmi_dag_release_fn release, void* user) {
+    return createFromMeshes(params, meshes, meshCount, instances, instanceCount, view, nullptr, build, release, user);
+}
+brmi_scene* brmi_scene_create_from_meshes_with_materials(const brmi_scene_params* params, const brmi_mesh_input* meshes, uint32_t meshCount, const brmi_instance_input* instances,
+                                                         uint32_t instanceCount, const brmi_view_input* view, const brmi_material_inputs* materials,
+                                                         brmi_dag_build_fn build, brmi_dag_release_fn release, void* user) {
+    if (!materials) return nullptr;
+    return createFromMeshes(params, meshes, meshCount, instances, instanceCount, view, materials, build, release, user);
 }
 brmi_scene* brmi_scene_create_with_dag_builder(const brmi_scene_params* params, brmi_dag_build_fn build, brmi_dag_release_fn release, void* user) {
     if (!params || params->lodBuilder != BRMI_LOD_BUILDER_EXTERNAL || !build) return nullptr;

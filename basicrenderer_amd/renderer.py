@@ -74,6 +74,8 @@ class VisibilityRenderer:
         self._check(self.lib.brmi_create(C.byref(cfg), C.byref(self._h)), "brmi_create", use_pass=False)
         self.sb, self._scene_keep = scene.device_buffers(self.device)
         self.device_arrays = dict(scene.device_arrays)      # this pass's own copies (two passes in flight each have their camera buffers)
+        if getattr(scene, "pending_chains", None):
+            self.build_texture_chains()
         self._check(self.lib.brmi_set_scene(self._h, C.byref(self.sb)), "brmi_set_scene")
         self._anisotropy = None      # set_anisotropy's table
         self._environment, self._environment_index = None, 0      # set_environment's device tables, perFrame.activeEnvironmentIndex of this pass's frames
@@ -100,6 +102,36 @@ class VisibilityRenderer:
     # ------------------------------------------------------------------------------------------
     def _s(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def texels(self):
+        """The device tensor of the scene's texel array (every texture's packed chain), or None for a scene without textures."""
+        return self.device_arrays.get("texels")
+
+    def build_texture_chains(self):
+        """Levels 1.. of every texture in scene.pending_chains, built in this pass's texel buffer by brmi_texmips_build / brmi_texmips_build_alpha
+        (DESIGN.md 4.13), and copied back into scene.arrays["texels"]: the host arrays (what the CPU oracle reads, what a later pass uploads) then hold
+        the chains the device built, and the list is emptied."""
+        torch, scene = self.torch, self.scene
+        texels = self.texels()
+        descs = scene.arrays["textureDescs"].view(np.uint8).reshape(-1, 96)
+        table = self.device_arrays["srgbToLinear"]
+        scratch = torch.zeros(4, dtype=torch.uint8, device=self.device)
+        keep = []
+        for index, alpha in scene.pending_chains:
+            d = capi.TextureDesc.from_buffer_copy(descs[index].tobytes())
+            d.texels = texels.data_ptr() + int(descs[index, :8].view(np.uint64)[0])
+            if alpha:
+                stats = torch.zeros(d.mipCount * 260, dtype=torch.int32, device=self.device)
+                scales = torch.zeros(d.mipCount, dtype=torch.float32, device=self.device)
+                keep += [stats, scales]
+                rc = self.lib.brmi_texmips_build_alpha(C.byref(d), table.data_ptr(), stats.data_ptr(), scales.data_ptr(), self._s())
+            else:
+                rc = self.lib.brmi_texmips_build(C.byref(d), table.data_ptr(), scratch.data_ptr(), 4, self._s())
+            if rc != 0:
+                raise BrmiError(f"texture {index}: mip chain build failed ({rc}): {self.lib.brmi_last_error(None).decode()}")
+        torch.cuda.synchronize(self.device)
+        scene.arrays["texels"] = texels.cpu().numpy().view(scene.arrays["texels"].dtype).reshape(scene.arrays["texels"].shape)
+        scene.pending_chains = []
 
     def _check(self, rc, what, use_pass=True):
         if rc != 0:

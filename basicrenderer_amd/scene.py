@@ -35,13 +35,17 @@ TEXTURE_DESC_BYTES = 96      # brmi_texture_desc; its first 8 bytes are the texe
 class Scene:
     def __init__(self, preset="sponza", width=3840, height=2160, seed=0, point_lights=64, directional=True,
                  lod_levels=0, size_scale=1.0, material_features=0, camera_step=0, skinned_fraction=0.0, lod_builder="quadtree", spot_every=0, cache_dir=None, export_cache=None,
-                 detail=1.0, unique_budget=False, relief_slope=0.0, dag_builder=None, meshes=None, instances=None, view=None):
+                 detail=1.0, unique_budget=False, relief_slope=0.0, dag_builder=None, meshes=None, instances=None, view=None, materials=None):
         """lod_builder: "quadtree" (regular grid DAG) or "own" (the library's cluster-LOD builder); dag_builder = (build_fn, release_fn)
         addresses of a caller-supplied builder with the brmi_dag_build_fn / brmi_dag_release_fn signatures (lod_builder becomes "external").
 
         meshes / instances / view: a scene of the CALLER's geometry (brmi_scene_create_from_meshes) instead of a preset.  meshes = list of
         dicts {positions [V,3] f32, indices [T*3] u32, normals / uvs / colors optional, material}; instances = list of (mesh index, 4x4
-        row-vector model matrix[, reverse_winding]); view = dict(eye, yaw, pitch, fov, near, far)."""
+        row-vector model matrix[, reverse_winding]); view = dict(eye, yaw, pitch, fov, near, far).
+        materials (with meshes): the caller's own materials (brmi_scene_create_from_meshes_with_materials) as gltf.load_gltf_materials returns them:
+        dict(materials, textures = [dict(texels (h, w, 4) uint8, srgb, alpha_coverage)], samplers); a mesh's "uvs1" is its second UV set.  The scene's texture
+        chains come out with levels 1.. empty; `pending_chains` lists (texture index, alpha_coverage) for VisibilityRenderer.build_texture_chains."""
+        self.pending_chains = []
         lib = capi.scene_lib()
         p = capi.SceneParams()
         p.preset = PRESETS[preset] if isinstance(preset, str) else int(preset)
@@ -87,7 +91,32 @@ class Scene:
             vi.eye[0], vi.eye[1], vi.eye[2] = (float(x) for x in view["eye"])
             vi.yaw, vi.pitch, vi.fovYDegrees, vi.zNear, vi.zFar = float(view.get("yaw", 0.0)), float(view.get("pitch", 0.0)), float(view.get("fov", 60.0)), float(view.get("near", 0.1)), float(view.get("far", 1000.0))
             b = dag_builder if dag_builder is not None else (None, None)
-            self._h = lib.brmi_scene_create_from_meshes(C.byref(p), mi, len(meshes), ii, len(instances), C.byref(vi), b[0], b[1], None)
+            if materials is None:
+                self._h = lib.brmi_scene_create_from_meshes(C.byref(p), mi, len(meshes), ii, len(instances), C.byref(vi), b[0], b[1], None)
+            else:
+                mats = np.ascontiguousarray(materials["materials"]); samp = np.ascontiguousarray(materials["samplers"])
+                td = (capi.TextureDesc * max(1, len(materials["textures"])))()
+                for k, t in enumerate(materials["textures"]):
+                    tx = np.ascontiguousarray(t["texels"], dtype=np.uint8); keep.append(tx)
+                    td[k].texels, td[k].height, td[k].width = tx.ctypes.data, tx.shape[0], tx.shape[1]
+                    td[k].mipCount = int(t.get("mips") or min(capi.TEXTURE_MAX_MIPS, int(max(tx.shape[0], tx.shape[1])).bit_length()))
+                    td[k].format = capi.TEXTURE_FORMAT_RGBA8_UNORM_SRGB if t.get("srgb") else capi.TEXTURE_FORMAT_RGBA8_UNORM
+                    if td[k].mipCount > 1:
+                        self.pending_chains.append((k, bool(t.get("alpha_coverage"))))
+                inp = capi.MaterialInputs()
+                inp.structSize = C.sizeof(capi.MaterialInputs)
+                inp.materials, inp.materialCount = mats.ctypes.data, len(mats)
+                inp.textures, inp.textureCount = C.cast(td, capi.vp), len(materials["textures"])
+                inp.samplers, inp.samplerCount = samp.ctypes.data, len(samp)
+                if any(m.get("uvs1") is not None for m in meshes):
+                    u1 = (capi.vp * len(meshes))()
+                    for k, m in enumerate(meshes):
+                        if m.get("uvs1") is not None:
+                            a = np.ascontiguousarray(m["uvs1"], dtype=np.float32).reshape(len(m["positions"]), 2); keep.append(a)      # (a wrong length raises here: the library reads vertexCount pairs)
+                            u1[k] = a.ctypes.data
+                    keep.append(u1)
+                    inp.uvs1 = C.cast(u1, capi.vp)
+                self._h = lib.brmi_scene_create_from_meshes_with_materials(C.byref(p), mi, len(meshes), ii, len(instances), C.byref(vi), C.byref(inp), b[0], b[1], None)
             if not self._h:
                 raise RuntimeError("brmi_scene_create_from_meshes failed: bad mesh / instance input")
             del keep
@@ -211,5 +240,7 @@ class Scene:
             if cnt:
                 setattr(sb, cnt, self.counts[arr])
         if self.counts["textureDescs"]:
-            sb.textures, sb.textureCount = up(self._relocated_texture_descs(up(self.arrays["texels"]))), self.counts["textureDescs"]
+            texel_base = up(self.arrays["texels"])
+            self.device_arrays["texels"] = keep[-1]
+            sb.textures, sb.textureCount = up(self._relocated_texture_descs(texel_base)), self.counts["textureDescs"]
         return sb, keep

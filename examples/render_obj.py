@@ -39,6 +39,7 @@ def main():
     ap.add_argument("--gtao", nargs="?", const="high", default=None, metavar="QUALITY", help="screen-space ambient occlusion (XeGTAO) in the environment term: low, medium, high (default) or ultra; "
                     "`--gtao --view ao` shows the visibility the shading takes")
     ap.add_argument("--view", default=None, metavar="NAME", help="write this debug view (e.g. meshlets) instead of the tone-mapped frame")
+    ap.add_argument("--procedural-materials", action="store_true", help="a glTF file's own materials and textures are used by default; this keeps the procedural stand-ins (--features)")
     a = ap.parse_args()
     from basicrenderer_amd import Scene
     from basicrenderer_amd.obj import frame_view, load_obj
@@ -48,10 +49,12 @@ def main():
         from basicrenderer_amd import gltf
         meshes, instances = gltf.load_gltf(a.obj)
         view = gltf.frame_view(meshes, instances)
+        materials = None if a.procedural_materials else gltf.load_gltf_materials(a.obj)
     else:
+        materials = None
         meshes = load_obj(a.obj)
         instances, view = [(k, np.eye(4, dtype=np.float32)) for k in range(len(meshes))], frame_view(meshes)
-    sc = Scene(width=w, height=h, point_lights=a.lights, material_features=a.features, meshes=meshes, instances=instances, view=view)
+    sc = Scene(width=w, height=h, point_lights=a.lights, material_features=a.features, meshes=meshes, instances=instances, view=view, materials=materials)
     r = VisibilityRenderer(sc, occlusion=True)
     if a.anisotropy > 0:
         r.set_anisotropy(a.anisotropy)

@@ -345,6 +345,30 @@ int brmi_env_prefilter(const brmi_texture_desc* sourceCube, const brmi_texture_d
                        brmi_stream stream);
 uint64_t brmi_env_build_bytes(uint32_t size, uint32_t levels, uint64_t* cubeBytes, uint64_t* prefilteredBytes);
 
+/* ---- texture mip chains: the reference's MipmappingPass -- mipmapping.hlsl over ffx_spd.h, alphaCoverageMipmapping.hlsl ---------------------
+ * Two stages on caller-owned DEVICE memory; they need no pass and allocate nothing.  `texture` is ONE descriptor in HOST memory, read during the call (the
+ * refusals below need its fields); its `texels` is a device pointer to the whole packed chain (brmi_types.h: level l is max(1, w >> l) x max(1, h >> l) RGBA8
+ * texels, mipOffset[l] texels after `texels`) with level 0 filled.  Levels 1 .. mipCount - 1 are written, every texel of them; level 0 and everything outside the
+ * levels are not touched.  mipCount == 1 launches nothing.  `srgbToLinear`: the scene's float[256] decode table (device); with BRMI_TEXTURE_FORMAT_RGBA8_UNORM_SRGB
+ * level 0's rgb is decoded through it and every stored level is encoded with LinearToSrgb of the shader text.
+ *
+ * brmi_texmips_build        the plain chain (SPD's Float4 variant), one launch.  `scratch`: brmi_texmips_bytes' scratchBytes, ZERO before the first build;
+ *                           the build leaves it zero, so it serves every later build on the same stream without a clear.  Width and height <= 4096.
+ * brmi_texmips_build_alpha  the alpha-coverage chain: per level reset, downsample + statistics, scale, apply.  `stats` (260 words per level: covered and total
+ *                           count of the source level, destination count, 256-bin histogram, one pad) and `scales` (one float per level) are outputs the
+ *                           caller may read; the words of level 0 are not written.
+ * brmi_texmips_bytes        the three sizes for a chain of mipCount levels; returns their sum (0 for a refused mipCount).  Any pointer may be null.
+ *
+ * The alpha chain has no size limit of its own, and `stats` / `scales` come without byte counts: the caller is trusted to have sized them with
+ * brmi_texmips_bytes, as it is trusted with the chain's own allocation.
+ * Refused before any launch, with the reason in brmi_last_error(NULL): a null pass reads the calling thread's last stage refusal ("null pass" when there is
+ * none; a stage call that succeeds clears it): BRMI_ERR_INVALID for a null or misaligned (4 B) pointer, a format
+ * other than the two RGBA8 ones, an empty image, mipCount 0 or above BRMI_TEXTURE_MAX_MIPS or longer than the size allows, levels that overlap;
+ * BRMI_ERR_CAPACITY for scratch that is too small or (plain chain) an image beyond 4096 texels. */
+uint64_t brmi_texmips_bytes(uint32_t mipCount, uint64_t* scratchBytes, uint64_t* statsBytes, uint64_t* scalesBytes);
+int brmi_texmips_build(const brmi_texture_desc* texture, const float* srgbToLinear, void* scratch, uint64_t scratchBytes, brmi_stream stream);
+int brmi_texmips_build_alpha(const brmi_texture_desc* texture, const float* srgbToLinear, uint32_t* stats, float* scales, brmi_stream stream);
+
 /* ---- XeGTAO ambient occlusion: the reference's BuildGTAOPipeline -- GTAOFilterPass, GTAOMainPass, GTAODenoisePass -----------------------
  * Off by default: a pass that never calls brmi_set_gtao, or calls it with NULL, launches exactly what it launched before and writes the same bytes.  With it
  * bound, brmi_execute / brmi_execute_split run the three stages between the G-buffer stage and the shading stage (on the shading stream, inside the shading

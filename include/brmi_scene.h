@@ -153,6 +153,27 @@ brmi_scene* brmi_scene_create_from_meshes(const brmi_scene_params* params, const
                                           const brmi_instance_input* instances, uint32_t instanceCount, const brmi_view_input* view,
                                           brmi_dag_build_fn build, brmi_dag_release_fn release, void* user);
 
+/* The same scene with the CALLER's materials where the procedural ones go.  `materials` index as brmi_mesh_input::material does (a mesh naming a
+ * material >= materialCount is refused); `openpbr` may be empty: every material then gets a base layer of its own factors and openPBRMaterialDataIndex = its index.
+ * A texture descriptor's `texels` is a HOST pointer to width x height RGBA8 level-0 texels; width, height, format (one of the two RGBA8 formats) and mipCount
+ * (1 .. what the size allows) are read, mipOffset is not.  The scene's descriptors come out with the whole packed chain reserved (mipOffset filled), level 0
+ * copied and levels 1.. ZERO: the harness fills them on the device with brmi_texmips_build / brmi_texmips_build_alpha after upload.  Pages carry UV set 0
+ * (brmi_mesh_input::uvs) and, when a material names set 1, set 1 from `uvs1` (one pointer per mesh, vertexCount x 2, or NULL for a mesh or for all: set 1 is
+ * then the affine image of set 0 the procedural scenes use).  params->materialFeatures: only bit 5 (vertex colours) is read.  A slot that a material's flags
+ * switch on must name a texture < textureCount and a sampler < samplerCount: a dangling index is refused here (the kernels would read it as "not bound", as they do
+ * for any scene).  NULL on bad input. */
+typedef struct brmi_material_inputs {
+    uint32_t structSize, reserved;
+    const brmi_material_info*         materials;  uint32_t materialCount;  uint32_t openpbrCount;
+    const brmi_openpbr_material_info* openpbr;
+    const brmi_texture_desc*          textures;   uint32_t textureCount;   uint32_t samplerCount;
+    const brmi_sampler_desc*          samplers;
+    const float* const*               uvs1;
+} brmi_material_inputs;
+brmi_scene* brmi_scene_create_from_meshes_with_materials(const brmi_scene_params* params, const brmi_mesh_input* meshes, uint32_t meshCount,
+                                                         const brmi_instance_input* instances, uint32_t instanceCount, const brmi_view_input* view,
+                                                         const brmi_material_inputs* materials, brmi_dag_build_fn build, brmi_dag_release_fn release, void* user);
+
 /* This library's cluster-LOD builder, with the brmi_dag_build_fn / brmi_dag_release_fn signatures (user is ignored).
  * Limits 128 vertices / 128 triangles per cluster, groups of ~384 clusters with <= 8 refined groups each, target ratio 0.5, stuck
  * threshold 0.85, error merge max(1.5 x previous, current): the settings of BR/src/Mesh/ClusterLODUtilities.cpp:5426-5458. */
