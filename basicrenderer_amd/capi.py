@@ -150,6 +150,29 @@ class GtaoBuffers(C.Structure):
     _fields_ = [("structSize", u32), ("reserved", u32), ("settings", GtaoSettings), ("scratch", vp), ("scratchBytes", u64), ("aoTerm", vp), ("aoTermBytes", u64)]
 
 
+class DisplaySettings(C.Structure):
+    """brmi_display_settings (include/brmi.h), 48 B."""
+    _fields_ = [("structSize", u32), ("tonemapType", u32), ("bloom", u32), ("autoExposure", u32), ("minLogLuminance", f32), ("logLuminanceRange", f32),
+                ("timeCoefficient", f32), ("fixedAdaptedLuminance", f32), ("reserved", u32 * 4)]
+
+
+class DisplayPlane(C.Structure):
+    _fields_ = [("offset", u64), ("bytes", u64), ("width", u32), ("height", u32)]
+
+
+class DisplayLayout(C.Structure):
+    """brmi_display_layout (include/brmi.h): where the display chain's state and bloom levels lie in the caller's scratch, 176 B."""
+    _fields_ = [("bloom", DisplayPlane * 5), ("bloomLevels", u32), ("reserved", u32), ("histogramOffset", u64), ("adaptedLuminanceOffset", u64),
+                ("controlBlockOffset", u64), ("scratchBytes", u64), ("ldrBytes", u64), ("blendedHdrBytes", u64)]
+
+
+class DisplayBuffers(C.Structure):
+    """brmi_display_buffers (include/brmi.h): the settings and the caller-owned device memory of the display chain, 104 B."""
+    _fields_ = [("structSize", u32), ("reserved", u32), ("settings", DisplaySettings), ("scratch", vp), ("scratchBytes", u64), ("ldr", vp), ("ldrBytes", u64),
+                ("blendedHdr", vp), ("blendedHdrBytes", u64)]
+
+
+TONEMAP_TYPES = {"reinhard": 0, "neutral": 1, "aces": 2, "lpm": 3, "none": 4}      # the reference's tonemapType setting; 4 is the switch's default
 GTAO_QUALITY = {"low": 0, "medium": 1, "high": 2, "ultra": 3}      # slices x steps: 1 x 2, 2 x 2, 3 x 3, 9 x 3
 
 
@@ -306,7 +329,8 @@ BRMI_EXPORTS = ["brmi_abi_version", "brmi_default_config", "brmi_create", "brmi_
                 "brmi_set_environment", "brmi_debug_ibl_lookup", "brmi_debug_ibl",
                 "brmi_skybox", "brmi_env_convert", "brmi_env_project_sh", "brmi_env_prefilter", "brmi_env_build_bytes", "brmi_debug_env_lookup",
                 "brmi_gtao_default_settings", "brmi_gtao_get_layout", "brmi_set_gtao", "brmi_gtao_prefilter", "brmi_gtao_main", "brmi_gtao_denoise",
-                "brmi_texmips_bytes", "brmi_texmips_build", "brmi_texmips_build_alpha"]
+                "brmi_texmips_bytes", "brmi_texmips_build", "brmi_texmips_build_alpha",
+                "brmi_display_default_settings", "brmi_display_get_layout", "brmi_set_display", "brmi_display_exposure", "brmi_display_bloom", "brmi_display_resolve", "brmi_debug_display_bloom_pass", "brmi_debug_display_histogram"]
 
 
 def brmi_lib():
@@ -386,5 +410,13 @@ def brmi_lib():
             lib.brmi_texmips_bytes.restype = u64
             lib.brmi_texmips_build.argtypes = [C.POINTER(TextureDesc), vp, vp, u64, vp]
             lib.brmi_texmips_build_alpha.argtypes = [C.POINTER(TextureDesc), vp, vp, vp, vp]
+        if hasattr(lib, "brmi_set_display"):
+            lib.brmi_display_default_settings.argtypes = [C.POINTER(DisplaySettings)]
+            lib.brmi_display_default_settings.restype = None
+            lib.brmi_display_get_layout.argtypes = [u32, u32, C.POINTER(DisplayLayout)]
+            lib.brmi_set_display.argtypes = [vp, C.POINTER(DisplayBuffers)]
+            for n in ("brmi_display_exposure", "brmi_display_bloom", "brmi_display_resolve", "brmi_debug_display_histogram"):
+                getattr(lib, n).argtypes = [vp, vp]
+            lib.brmi_debug_display_bloom_pass.argtypes = [vp, u32, u32, vp]
         _brmi_lib = lib
     return _brmi_lib

@@ -18,6 +18,7 @@
 #include <cstring>
 
 #include "brmi_device.h"
+#include "brmi_display_math.h"
 #include "brmi_internal.h"
 
 namespace brmi {
@@ -763,6 +764,84 @@ int brmi_gtao_denoise(brmi_pass* p, brmi_stream stream) {
     if (int rc = gtao_refusal(p, "brmi_gtao_denoise")) return rc;
     return brmi::launch_gtao_denoise(p, static_cast<hipStream_t>(stream));
 }
+// ---- the display chain (brmi_display.hip): every refusal comes before the first launch
+void brmi_display_default_settings(brmi_display_settings* s) {
+    if (!s) return;
+    *s = brmi_display_settings{};
+    s->structSize = (uint32_t)sizeof(brmi_display_settings); s->tonemapType = 3u; s->bloom = 1u; s->autoExposure = 1u;
+    s->minLogLuminance = brmi::display::kMinLogLuminance; s->logLuminanceRange = brmi::display::default_log_luminance_range();
+    s->timeCoefficient = 1.0f / 60.0f; s->fixedAdaptedLuminance = 0.18f;
+}
+int brmi_display_get_layout(uint32_t width, uint32_t height, brmi_display_layout* layout) {
+    if (!layout || width == 0u || height == 0u) return BRMI_ERR_INVALID;
+    brmi::display_layout(width, height, layout);
+    return BRMI_OK;
+}
+int brmi_set_display(brmi_pass* p, const brmi_display_buffers* b) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (!b) { p->display.on = false; p->display.b = brmi_display_buffers{}; return BRMI_OK; }
+    if (b->structSize != sizeof(brmi_display_buffers)) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_display: structSize %u, expected %zu", b->structSize, sizeof(brmi_display_buffers));
+    const brmi_display_settings& st = b->settings;
+    if (st.structSize != sizeof(brmi_display_settings)) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_display: settings.structSize %u, expected %zu", st.structSize, sizeof(brmi_display_settings));
+    // the histogram is frame-wide and the bloom taps cross rows: no partition of the frame
+    if (p->cfg.bandY0 != 0u || (p->cfg.bandY1 != 0u && p->cfg.bandY1 < p->cfg.height) || p->bandY0 != 0u || p->bandY1 < p->cfg.height || p->cfg.dynamicBand || p->stripes.count > 1u)
+        return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_display: not with a row band, dynamicBand or the interleaved partition (the histogram is frame-wide, the bloom taps cross rows)");
+    if (st.tonemapType > 4u) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_display: tonemapType %u (0..4)", st.tonemapType);
+    if (st.bloom > 1u || st.autoExposure > 1u) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_display: bloom %u and autoExposure %u are 0 or 1", st.bloom, st.autoExposure);
+    if (st.reserved[0] || st.reserved[1] || st.reserved[2] || st.reserved[3] || b->reserved) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_display: a reserved word is not zero");
+    if (!std::isfinite(st.minLogLuminance) || !std::isfinite(st.logLuminanceRange) || !std::isfinite(st.timeCoefficient) || !std::isfinite(st.fixedAdaptedLuminance))
+        return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_display: a setting is not finite");
+    if (!(st.logLuminanceRange > 0.0f)) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_display: logLuminanceRange %g must be > 0", (double)st.logLuminanceRange);
+    if (st.bloom && !brmi::display::bloom_possible(p->cfg.width, p->cfg.height))
+        return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_display: bloom needs 32 pixels a side, the frame is %u x %u (a level would have no rows)", p->cfg.width, p->cfg.height);
+    brmi_display_layout l; brmi::display_layout(p->cfg.width, p->cfg.height, &l);
+    if (!b->scratch || !b->ldr) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_display: a null buffer");
+    if ((reinterpret_cast<uintptr_t>(b->scratch) & 15u) || (reinterpret_cast<uintptr_t>(b->blendedHdr) & 15u) || (reinterpret_cast<uintptr_t>(b->ldr) & 3u))
+        return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_display: scratch and blendedHdr must be 16 B aligned, ldr 4 B");
+    if (b->scratchBytes < l.scratchBytes) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_display: scratch holds %llu bytes, %u x %u pixels need %llu", (unsigned long long)b->scratchBytes, p->cfg.width, p->cfg.height, (unsigned long long)l.scratchBytes);
+    if (b->ldrBytes < l.ldrBytes) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_display: ldr holds %llu bytes, %u x %u pixels need %llu", (unsigned long long)b->ldrBytes, p->cfg.width, p->cfg.height, (unsigned long long)l.ldrBytes);
+    if (b->blendedHdr && b->blendedHdrBytes < l.blendedHdrBytes)
+        return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_display: blendedHdr holds %llu bytes, %u x %u pixels need %llu", (unsigned long long)b->blendedHdrBytes, p->cfg.width, p->cfg.height, (unsigned long long)l.blendedHdrBytes);
+    p->display.b = *b; p->display.layout = l; p->display.on = true;
+    return BRMI_OK;
+}
+// what keeps a display stage from running (host state only: brmi_execute_split asks before the frame's first launch)
+static int display_refusal(brmi_pass* p, const char* what) {
+    if (!p->setupDone || !p->updated) return brmi::fail(p, BRMI_ERR_STATE, "%s: setup/update not done", what);
+    if (!p->display.on) return brmi::fail(p, BRMI_ERR_STATE, "%s: no display buffers bound (brmi_set_display)", what);
+    if (p->bandY0 != 0u || p->bandY1 < p->cfg.height) return brmi::fail(p, BRMI_ERR_STATE, "%s: the pass renders a row band", what);
+    if (!p->res[BRMI_RES_HDR_COLOR]) return brmi::fail(p, BRMI_ERR_STATE, "%s: the HDR surface is not bound", what);
+    return BRMI_OK;
+}
+int brmi_display_exposure(brmi_pass* p, brmi_stream stream) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (int rc = display_refusal(p, "brmi_display_exposure")) return rc;
+    return brmi::launch_display_exposure(p, static_cast<hipStream_t>(stream));
+}
+int brmi_display_bloom(brmi_pass* p, brmi_stream stream) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (int rc = display_refusal(p, "brmi_display_bloom")) return rc;
+    return brmi::launch_display_bloom(p, static_cast<hipStream_t>(stream));
+}
+int brmi_debug_display_histogram(brmi_pass* p, brmi_stream stream) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (int rc = display_refusal(p, "brmi_debug_display_histogram")) return rc;
+    if (!p->display.b.settings.autoExposure) return brmi::fail(p, BRMI_ERR_STATE, "brmi_debug_display_histogram: the binding has autoExposure off");
+    return brmi::launch_display_exposure(p, static_cast<hipStream_t>(stream), true);
+}
+int brmi_debug_display_bloom_pass(brmi_pass* p, uint32_t mipIndex, uint32_t isUpsample, brmi_stream stream) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (int rc = display_refusal(p, "brmi_debug_display_bloom_pass")) return rc;
+    if (!p->display.b.settings.bloom) return brmi::fail(p, BRMI_ERR_STATE, "brmi_debug_display_bloom_pass: the binding has bloom off");
+    if (isUpsample > 1u || mipIndex >= p->display.layout.bloomLevels || (isUpsample && mipIndex == 0u))
+        return brmi::fail(p, BRMI_ERR_INVALID, "brmi_debug_display_bloom_pass: mipIndex %u, isUpsample %u (down 0..%u, up 1..%u)", mipIndex, isUpsample, p->display.layout.bloomLevels - 1u, p->display.layout.bloomLevels - 1u);
+    return brmi::launch_display_bloom_pass(p, mipIndex, isUpsample != 0u, static_cast<hipStream_t>(stream));
+}
+int brmi_display_resolve(brmi_pass* p, brmi_stream stream) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (int rc = display_refusal(p, "brmi_display_resolve")) return rc;
+    return brmi::launch_display_resolve(p, static_cast<hipStream_t>(stream));
+}
 int brmi_streaming_feedback(brmi_pass* p, brmi_stream stream) {
     CHECK_READY(p);
     if (!p->streaming.on) return brmi::fail(p, BRMI_ERR_STATE, "brmi_streaming_feedback: no streaming buffers bound (brmi_set_streaming)");
@@ -852,6 +931,7 @@ int brmi_execute_split(brmi_pass* p, brmi_stream stream, brmi_stream shadeStream
     const bool skybox = p->env.on && p->env.b.skybox;      // ... and so is a skybox stage that could not run
     if (skybox && (rc = skybox_refusal(p))) return rc;
     if (p->gtao.on && (rc = gtao_refusal(p, "brmi_execute"))) return rc;      // ... and the GTAO stages of a bound term
+    if (p->display.on && (rc = display_refusal(p, "brmi_execute"))) return rc;      // ... and the display chain of a bound target
     p->executesSinceTimes++;
     const bool split = shadeStream != stream;
     if ((rc = wait_for_frames_in_flight(p, stream))) return rc;      // (once for the frame: the stage bodies below have none)
@@ -913,6 +993,11 @@ int brmi_execute_split(brmi_pass* p, brmi_stream stream, brmi_stream shadeStream
     if ((rc = stage_shade(p, ctx, stream, p->gtao.on))) return rc;
     // SkyboxRenderPass behind the deferred shading (the reference's Deferred -> Skybox -> Forward), only where the bound environment asks for it
     if (skybox && (rc = brmi_skybox(p, stream))) return rc;
+    // LuminanceHistogram(+Average)Pass, BuildBloomPipeline and TonemappingPass behind the lit frame, on the shading stream, in front of the frame's end
+    if (p->display.on) {
+        hipStream_t ds = static_cast<hipStream_t>(stream);
+        if ((rc = brmi::launch_display_exposure(p, ds)) || (rc = brmi::launch_display_bloom(p, ds)) || (rc = brmi::launch_display_resolve(p, ds))) return rc;
+    }
     // the debug payload of perFrame.outputType, from the surfaces the frame has just made (behind the shading stage, on its stream, in front of the frame's end)
     if (debugView && (rc = brmi_debug_view(p, stream))) return rc;
     if (split) { BRMI_HIP(p, hipEventRecord(p->frameDone, static_cast<hipStream_t>(stream))); p->frameDoneRecorded = true; }

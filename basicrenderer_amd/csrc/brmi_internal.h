@@ -397,6 +397,7 @@ struct brmi_pass {
     struct { bool on = false; brmi_debug_view_buffers b{}; } debugView;      // brmi_set_debug_view
     struct { bool on = false; brmi_environment_buffers b{}; } env;      // brmi_set_environment (kept by brmi_set_scene: nothing of it depends on the scene)
     struct { bool on = false; brmi_gtao_buffers b{}; brmi_gtao_layout layout{}; } gtao;      // brmi_set_gtao (kept by brmi_set_scene: sized by the frame alone)
+    struct { bool on = false; brmi_display_buffers b{}; brmi_display_layout layout{}; } display;      // brmi_set_display (kept by brmi_set_scene: sized by the frame alone)
     uint32_t frameIndexHost = 0;                 // brmi_frame_update::frameIndex of the last brmi_update (the GTAO noise's temporal index)
     const uint32_t* samplerAniso = nullptr;      // brmi_set_sampler_anisotropy: device words, one per sampler of the scene (cleared by brmi_set_scene)
     brmi_camera camHost{};
@@ -457,6 +458,12 @@ void gtao_layout(uint32_t width, uint32_t height, brmi_gtao_layout* l);
 int launch_gtao_prefilter(brmi_pass* p, hipStream_t s);
 int launch_gtao_main(brmi_pass* p, hipStream_t s);
 int launch_gtao_denoise(brmi_pass* p, hipStream_t s);
+// brmi_display.hip (the entry points have checked the binding)
+void display_layout(uint32_t width, uint32_t height, brmi_display_layout* l);
+int launch_display_exposure(brmi_pass* p, hipStream_t s, bool histogramOnly = false);      // (histogramOnly: LuminanceHistogramPass alone, for tests)
+int launch_display_bloom(brmi_pass* p, hipStream_t s);
+int launch_display_bloom_pass(brmi_pass* p, uint32_t mipIndex, bool isUpsample, hipStream_t s);
+int launch_display_resolve(brmi_pass* p, hipStream_t s);
 int launch_env_convert(const brmi_texture_desc* equirect, const brmi_texture_desc* cube, uint32_t size, hipStream_t s);
 int launch_env_project_sh(const brmi_texture_desc* cubemaps, uint32_t cubemapCount, brmi_environment_info* env, uint32_t size, hipStream_t s);
 int launch_env_prefilter(const brmi_texture_desc* source, const brmi_texture_desc* prefiltered, uint32_t size, uint32_t levels, hipStream_t s);

@@ -150,6 +150,17 @@ BRMI_STAGE_PASS(DeferredShadingPass, "DeferredShadingPass", brmi_shade(state->ge
                   "Builtin::GBuffer::MetallicRoughness", "Builtin::PrimaryCamera::LinearDepthMap", "Builtin::Light::ClusterBuffer", "Builtin::Light::PagesBuffer",
                   "Builtin::OpenPBR::*"}),
                 ({"Builtin::Color::HDRColorTarget"}))
+// reference: the display chain behind the lit frame (BR/src/Renderer.cpp:2667-2704, RenderGraphBuildHelper.h:504-530).  Five reference passes, three stages:
+//   LuminanceHistogramPass + LuminanceHistogramAveragePass                                   -> brmi_display_exposure
+//   BloomDownsamplePass0..4 + BloomUpsamplePass4..1                                          -> brmi_display_bloom
+//   BloomUpsampleAndBlendPass + TonemappingPass (the blend is applied on the way, HDR kept)   -> brmi_display_resolve
+// The buffers are the graph's (brmi_set_display on PassState's handle, brmi_display_get_layout for their sizes); off until they are bound.
+BRMI_STAGE_PASS(LuminanceHistogramPass, "LuminanceHistogramPass", brmi_display_exposure(state->get(), ctx.commandList),
+                ({"Builtin::Color::HDRColorTarget"}), ({"Builtin::PostProcessing::LuminanceHistogram", "Builtin::PostProcessing::AdaptedLuminance", "FFX::LPMConstants"}))
+BRMI_STAGE_PASS(BloomPass, "BloomDownsamplePass0", brmi_display_bloom(state->get(), ctx.commandList),
+                ({"Builtin::Color::HDRColorTarget"}), ({"Builtin::PostProcessing::UpscaledHDR(mips 1-5)"}))
+BRMI_STAGE_PASS(TonemappingPass, "TonemappingPass", brmi_display_resolve(state->get(), ctx.commandList),
+                ({"Builtin::Color::HDRColorTarget", "Builtin::PostProcessing::UpscaledHDR(mip 1)", "FFX::LPMConstants"}), ({"back buffer (R8G8B8A8_UNorm)", "Builtin::PostProcessing::UpscaledHDR"}))
 #undef BRMI_STAGE_PASS
 #undef BRMI_STAGE_PASS_WITH
 

@@ -501,6 +501,85 @@ class VisibilityRenderer:
         self.torch.cuda.synchronize(self.device)
         return detile(self._gtao["term"][: int(self._gtao["layout"].outputBytes)].cpu().numpy(), self.W, self.H)
 
+    # -- the display chain (brmi_set_display) -------------------------------------------------------
+    def display_layout(self):
+        """capi.DisplayLayout of this pass's frame: where the histogram, the adapted luminance, the LPM control block and the bloom levels lie in the scratch."""
+        lay = capi.DisplayLayout()
+        self._check(self.lib.brmi_display_get_layout(capi.u32(self.W), capi.u32(self.H), C.byref(lay)), "brmi_display_get_layout", use_pass=False)
+        return lay
+
+    def set_display(self, tonemap="lpm", bloom=True, auto_exposure=True, time_coefficient=1.0 / 60.0, fixed_luminance=0.18, fill=0, guard=0):
+        """The displayed picture from the next frame on: execute() runs auto-exposure, the bloom pyramid and the tone mapper behind the lit frame, and ldr()
+        returns RGBA8.  tonemap: "reinhard" | "neutral" | "aces" | "lpm" | "none" (or 0..4), None for off -- exactly the frames of a pass that never called
+        this.  Calling it again with a binding in place only changes the settings (the frame's delta time as time_coefficient, say): the buffers, and the
+        adapted luminance in them, stay.  The buffers are this pass's own tensors (every byte `fill` to start with except the histogram and the adapted
+        luminance, which are zero; `guard` more bytes behind each that the library is not told about: display_guards_intact())."""
+        torch = self.torch
+        d = getattr(self, "_display", None)
+        if tonemap is None:
+            if d is not None:
+                torch.cuda.synchronize(self.device)
+            self._check(self.lib.brmi_set_display(self._h, None), "brmi_set_display")
+            self._display = None
+            return
+        if d is None:
+            lay = self.display_layout()
+            d = dict(layout=lay, fill=int(fill),
+                     scratch=torch.full((int(lay.scratchBytes) + int(guard),), int(fill), dtype=torch.uint8, device=self.device),
+                     ldr=torch.full((int(lay.ldrBytes) + int(guard),), int(fill), dtype=torch.uint8, device=self.device),
+                     blended=torch.full((int(lay.blendedHdrBytes) + int(guard),), int(fill), dtype=torch.uint8, device=self.device))
+            d["scratch"][int(lay.histogramOffset): int(lay.histogramOffset) + 1024].zero_()
+            d["scratch"][int(lay.adaptedLuminanceOffset): int(lay.adaptedLuminanceOffset) + 4].zero_()
+        lay = d["layout"]
+        b = capi.DisplayBuffers()
+        b.structSize = C.sizeof(capi.DisplayBuffers)
+        self.lib.brmi_display_default_settings(C.byref(b.settings))
+        b.settings.tonemapType = capi.TONEMAP_TYPES[tonemap.lower()] if isinstance(tonemap, str) else int(tonemap)
+        b.settings.bloom, b.settings.autoExposure = int(bool(bloom)), int(bool(auto_exposure))
+        b.settings.timeCoefficient, b.settings.fixedAdaptedLuminance = float(time_coefficient), float(fixed_luminance)
+        b.scratch, b.scratchBytes, b.ldr, b.ldrBytes = d["scratch"].data_ptr(), int(lay.scratchBytes), d["ldr"].data_ptr(), int(lay.ldrBytes)
+        b.blendedHdr, b.blendedHdrBytes = d["blended"].data_ptr(), int(lay.blendedHdrBytes)
+        self._check(self.lib.brmi_set_display(self._h, C.byref(b)), "brmi_set_display")
+        d["buffers"], d["bloom"] = b, bool(bloom)
+        self._display = d
+
+    def _displayed(self, what):
+        if getattr(self, "_display", None) is None:
+            raise BrmiError(f"{what}: set_display first")
+        self.torch.cuda.synchronize(self.device)
+        return self._display
+
+    def display_guards_intact(self):
+        """True while the guard bytes behind set_display's three buffers still hold their fill."""
+        d = self._displayed("display_guards_intact")
+        lay = d["layout"]
+        return all(bool((d[k][int(n):] == d["fill"]).all()) for k, n in (("scratch", lay.scratchBytes), ("ldr", lay.ldrBytes), ("blended", lay.blendedHdrBytes)))
+
+    def ldr(self):
+        """(H, W, 4) uint8: the last frame as the tone mapper stored it (R8G8B8A8_UNORM, alpha 255)."""
+        d = self._displayed("ldr")
+        return d["ldr"][: self.W * self.H * 4].cpu().numpy().reshape(self.H, self.W, 4)
+
+    def blended_hdr(self):
+        """(H, W) uint64: the lit frame with the bloom blended in (four halves a pixel), what the reference leaves in its upscaled HDR target.  Bloom only."""
+        d = self._displayed("blended_hdr")
+        if not d["bloom"]:
+            raise BrmiError("blended_hdr: the display chain runs without bloom")
+        return detile(d["blended"][: int(d["layout"].blendedHdrBytes)].cpu().numpy().view(np.uint64), self.W, self.H)
+
+    def adapted_luminance(self):
+        """The adapted luminance the last frame's average stage left: the only state the chain carries from frame to frame."""
+        d = self._displayed("adapted_luminance")
+        o = int(d["layout"].adaptedLuminanceOffset)
+        return float(d["scratch"][o: o + 4].cpu().numpy().view(np.float32)[0])
+
+    def reset_exposure(self):
+        """Adaptation starts again from zero (and from an empty histogram), as on the first frame."""
+        d = self._displayed("reset_exposure")
+        lay = d["layout"]
+        d["scratch"][int(lay.histogramOffset): int(lay.histogramOffset) + 1024].zero_()
+        d["scratch"][int(lay.adaptedLuminanceOffset): int(lay.adaptedLuminanceOffset) + 4].zero_()
+
     # -- debug views (brmi_set_debug_view, perFrame.outputType) ------------------------------------
     def set_debug_view(self, mode, fill=0, check=True):
         """The debug view of the frames from the next update() on: a perFrame.outputType number or the reference's name without the OUTPUT_ prefix
@@ -591,6 +670,7 @@ class VisibilityRenderer:
             self._debug_view = None
             self._environment = None
             self._gtao = None
+            self._display = None
             self._scene_keep = []
             self.device_arrays = {}
             if hasattr(self.scene, "device_arrays"):

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Render a Wavefront OBJ or a glTF 2.0 file (.gltf / .glb) through the whole path on an MI355X and write the lit frame as a PNG
-(Reinhard + sRGB).
+(Reinhard + sRGB), or -- with --tonemap -- the RGBA8 picture of the library's display chain (auto-exposure, bloom, tone mapping).
 
     python examples/render_obj.py model.obj|scene.glb out.png [--size 1920x1080] [--lights 32] [--features 0] [--environment sky] [--gtao] [--view NAME]
+                                  [--tonemap reinhard|neutral|aces|lpm|none] [--bloom] [--exposure-frames 8]
 
 --view NAME writes a debug view of the frame instead (perFrame.outputType: normal, albedo, metallic, roughness, emissive, ao, depth, meshlets,
 geometry_group, light_cluster_id, light_cluster_light_count, motion_vectors); pixels without geometry are black.
@@ -39,6 +40,9 @@ def main():
     ap.add_argument("--gtao", nargs="?", const="high", default=None, metavar="QUALITY", help="screen-space ambient occlusion (XeGTAO) in the environment term: low, medium, high (default) or ultra; "
                     "`--gtao --view ao` shows the visibility the shading takes")
     ap.add_argument("--view", default=None, metavar="NAME", help="write this debug view (e.g. meshlets) instead of the tone-mapped frame")
+    ap.add_argument("--tonemap", default=None, choices=["reinhard", "neutral", "aces", "lpm", "none"], help="write the RGBA8 of the library's display chain with this curve (default: off, the file as before)")
+    ap.add_argument("--bloom", action="store_true", help="with --tonemap: the bloom pyramid blended into the frame (both sides of the frame at least 32 pixels)")
+    ap.add_argument("--exposure-frames", type=int, default=8, metavar="N", help="with --tonemap: render N frames, the last N - 2 with time coefficient 1, so the auto-exposure has settled")
     ap.add_argument("--procedural-materials", action="store_true", help="a glTF file's own materials and textures are used by default; this keeps the procedural stand-ins (--features)")
     a = ap.parse_args()
     from basicrenderer_amd import Scene
@@ -68,6 +72,18 @@ def main():
         r.set_gtao(a.gtao)
     if a.view:
         r.set_debug_view(a.view)
+    if a.bloom and not a.tonemap:
+        ap.error("--bloom needs --tonemap")
+    if a.tonemap and a.view:
+        ap.error("--tonemap and --view write different pictures: give one of them")
+    if a.tonemap:
+        frames = max(a.exposure_frames, 1)
+        for k in range(frames):      # the first two frames bring the path's own history up; from then on the adaptation jumps to the frame's average
+            r.set_display(a.tonemap, bloom=a.bloom, time_coefficient=1.0 if k >= min(2, frames - 1) else 0.0)
+            r.execute()
+        write_png(a.png, np.ascontiguousarray(r.ldr()[..., :3]))
+        print(f"{a.obj}: {a.tonemap}{' + bloom' if a.bloom else ''}, adapted luminance {r.adapted_luminance():.4g} after {frames} frames -> {a.png}")
+        return
     r.execute(); r.execute()
     if a.view:
         write_png(a.png, np.ascontiguousarray(r.debug_image()[..., :3]))

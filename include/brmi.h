@@ -420,6 +420,69 @@ int  brmi_gtao_prefilter(brmi_pass* pass, brmi_stream stream);
 int  brmi_gtao_main(brmi_pass* pass, brmi_stream stream);
 int  brmi_gtao_denoise(brmi_pass* pass, brmi_stream stream);
 
+/* ---- The display chain: the reference's LuminanceHistogramPass, LuminanceHistogramAveragePass, BuildBloomPipeline and TonemappingPass --------
+ * Off by default: a pass that never calls brmi_set_display, or calls it with NULL, launches exactly what it launched before and writes the same bytes.  With it
+ * bound, brmi_execute / brmi_execute_split run brmi_display_exposure, brmi_display_bloom and brmi_display_resolve behind the skybox stage, on the shading stream,
+ * inside the shading half's ordering: `ldr` is ready when the shading stream is.  The pass's HDR target is only read.
+ *
+ * tonemapType        0 Reinhard-Jodie, 1 Khronos PBR Neutral, 2 ACES (Hill), 3 AMD LPM (the default, as the reference's `tonemapType` setting), 4 none (gamma only)
+ * bloom              1: five downsamples (level l is (W >> l) x (H >> l), l = 1 .. min(5, floor(log2(max(W, H))) + 1)), the additive tent upsamples and the 0.04
+ *                    blend, which brmi_display_resolve applies on the way (blendedHdr, when given, receives the blended level 0).  Refused below 32 pixels a side.
+ * autoExposure       1: the 256-bin histogram and its average drive the adapted luminance, adapted += (average - adapted) * timeCoefficient (the reference passes
+ *                    the frame's delta time, unclamped), and the LPM control block follows it.  0: no histogram stage; fixedAdaptedLuminance feeds the block.
+ * minLogLuminance, logLuminanceRange   the histogram's range (defaults 0.001 and log2(10) - log2(0.1), the reference's).
+ * All memory is the caller's, none of it part of brmi_declare: `scratch` (brmi_display_get_layout: the histogram, the adapted-luminance float, the 96-word LPM
+ * control block, the bloom levels in the surfaces' tiled layout, whole tiles), `ldr` (row-major R8G8B8A8, W * H * 4 bytes), `blendedHdr` (optional, tiled
+ * RGBA16F).  The caller zeroes the histogram and the adapted luminance ONCE: the average stage leaves the histogram zero, and the adapted luminance is the only
+ * state carried from frame to frame.  Passes that render frames in turn may share one scratch only if their shading streams are the same stream.
+ * brmi_set_display is host-only and cheap: call it between frames with the same buffers to change settings (the frame's delta time, say).  brmi_set_scene keeps
+ * the binding.  It refuses with BRMI_ERR_INVALID, before anything is launched: a wrong structSize (buffers or settings), a null scratch or ldr, a scratch or
+ * blendedHdr not 16 B aligned, an ldr not 4 B aligned, short buffers, tonemapType > 4, bloom or autoExposure > 1, non-zero reserved words, a non-finite setting
+ * or a range <= 0, bloom with a side below 32, and a pass with a row band, dynamicBand or stripes (the histogram is frame-wide, the taps cross rows). */
+typedef struct brmi_display_settings {
+    uint32_t structSize;        /* sizeof(brmi_display_settings) */
+    uint32_t tonemapType;
+    uint32_t bloom;
+    uint32_t autoExposure;
+    float    minLogLuminance;
+    float    logLuminanceRange;
+    float    timeCoefficient;
+    float    fixedAdaptedLuminance;
+    uint32_t reserved[4];       /* zero */
+} brmi_display_settings;        /* 48 B */
+typedef struct brmi_display_plane { uint64_t offset, bytes; uint32_t width, height; } brmi_display_plane;      /* byte offset into the scratch, whole tiles */
+typedef struct brmi_display_layout {
+    brmi_display_plane bloom[5];        /* levels 1 .. 5 (RGBA16F, tiled); bytes 0 where the frame has fewer levels or bloom is refused */
+    uint32_t bloomLevels;               /* 0 where bloom is refused (a side below 32) */
+    uint32_t reserved;
+    uint64_t histogramOffset;           /* 256 words */
+    uint64_t adaptedLuminanceOffset;    /* one float */
+    uint64_t controlBlockOffset;        /* 96 words, 128 B aligned */
+    uint64_t scratchBytes;              /* what brmi_display_buffers::scratch must hold */
+    uint64_t ldrBytes;                  /* W * H * 4 */
+    uint64_t blendedHdrBytes;           /* 8 B per pixel, whole tiles */
+} brmi_display_layout;                  /* 176 B */
+typedef struct brmi_display_buffers {
+    uint32_t structSize;        /* sizeof(brmi_display_buffers) */
+    uint32_t reserved;
+    brmi_display_settings settings;
+    void*    scratch;    uint64_t scratchBytes;
+    void*    ldr;        uint64_t ldrBytes;
+    void*    blendedHdr; uint64_t blendedHdrBytes;      /* NULL: not written.  Written only with bloom on. */
+} brmi_display_buffers;         /* 104 B */
+void brmi_display_default_settings(brmi_display_settings* settings);
+int  brmi_display_get_layout(uint32_t width, uint32_t height, brmi_display_layout* layout);      /* BRMI_ERR_INVALID: a null layout or an empty frame */
+int  brmi_set_display(brmi_pass* pass, const brmi_display_buffers* buffers_or_NULL);
+/* The stages.  BRMI_ERR_STATE before brmi_setup / brmi_update, or when nothing is bound.  exposure: histogram + average + control block (autoExposure 0: the
+ * control block alone); bloom: the down- and upsamples into levels 1 .. 5 (bloom 0: nothing); resolve: blend, tone curve, gamma, the RGBA8 store. */
+int  brmi_display_exposure(brmi_pass* pass, brmi_stream stream);
+int  brmi_display_bloom(brmi_pass* pass, brmi_stream stream);
+int  brmi_display_resolve(brmi_pass* pass, brmi_stream stream);
+/* One of the reference's BloomSamplePass{mipIndex, isUpsample} on its own, for tests that hold the pyramid level by level: down (mipIndex 0 .. 4) writes level
+ * mipIndex + 1 from level mipIndex, level 0 being the pass's HDR target; up (mipIndex 1 .. 4) adds the tent of level mipIndex + 1 to level mipIndex. */
+int  brmi_debug_display_histogram(brmi_pass* pass, brmi_stream stream);      /* LuminanceHistogramPass alone: adds the frame's counts to the histogram */
+int  brmi_debug_display_bloom_pass(brmi_pass* pass, uint32_t mipIndex, uint32_t isUpsample, brmi_stream stream);
+
 /* Debug views.  brmi_set_debug_view binds the targets (NULL unbinds and gives exactly the frames of a pass that never called it); with a target bound and
  * perFrame.outputType != 0, brmi_execute / brmi_execute_split run brmi_debug_view behind the shading stage (on the shading stream); an outputType the stage
  * would refuse makes them fail BEFORE anything is launched.  The lit HDR frame and
