@@ -204,7 +204,14 @@ class MaterialInputs(C.Structure):
                 ("textures", vp), ("textureCount", u32), ("samplerCount", u32), ("samplers", vp), ("uvs1", vp)]
 
 
+class ShadowBuffers(C.Structure):
+    """brmi_shadow_buffers (include/brmi.h): caller-owned device tables of the spot / point shadow maps, 56 B."""
+    _fields_ = [("structSize", u32), ("reserved", u32), ("maps", vp), ("mapCount", u32), ("reserved0", u32), ("spotCameraIndices", vp), ("spotCount", u32),
+                ("reserved1", u32), ("pointCameraIndices", vp), ("pointCount", u32), ("reserved2", u32)]
+
+
 TEXTURE_FORMAT_RGBA8_UNORM, TEXTURE_FORMAT_RGBA8_UNORM_SRGB, TEXTURE_FORMAT_RGBA16_FLOAT = 0, 1, 2      # BRMI_TEXTURE_FORMAT_*
+TEXTURE_FORMAT_R32_FLOAT = 3
 TEXTURE_MAX_MIPS = 16
 ENVIRONMENT_BUFFERS_SIZE_V1 = 40
 
@@ -330,7 +337,8 @@ BRMI_EXPORTS = ["brmi_abi_version", "brmi_default_config", "brmi_create", "brmi_
                 "brmi_skybox", "brmi_env_convert", "brmi_env_project_sh", "brmi_env_prefilter", "brmi_env_build_bytes", "brmi_debug_env_lookup",
                 "brmi_gtao_default_settings", "brmi_gtao_get_layout", "brmi_set_gtao", "brmi_gtao_prefilter", "brmi_gtao_main", "brmi_gtao_denoise",
                 "brmi_texmips_bytes", "brmi_texmips_build", "brmi_texmips_build_alpha",
-                "brmi_display_default_settings", "brmi_display_get_layout", "brmi_set_display", "brmi_display_exposure", "brmi_display_bloom", "brmi_display_resolve", "brmi_debug_display_bloom_pass", "brmi_debug_display_histogram"]
+                "brmi_display_default_settings", "brmi_display_get_layout", "brmi_set_display", "brmi_display_exposure", "brmi_display_bloom", "brmi_display_resolve", "brmi_debug_display_bloom_pass", "brmi_debug_display_histogram",
+                "brmi_set_shadows", "brmi_shadow_capture", "brmi_debug_shadow"]
 
 
 def brmi_lib():
@@ -418,5 +426,9 @@ def brmi_lib():
             for n in ("brmi_display_exposure", "brmi_display_bloom", "brmi_display_resolve", "brmi_debug_display_histogram"):
                 getattr(lib, n).argtypes = [vp, vp]
             lib.brmi_debug_display_bloom_pass.argtypes = [vp, u32, u32, vp]
+        if hasattr(lib, "brmi_set_shadows"):
+            lib.brmi_set_shadows.argtypes = [vp, C.POINTER(ShadowBuffers)]
+            lib.brmi_shadow_capture.argtypes = [vp, f32, f32, C.POINTER(TextureDesc), vp]
+            lib.brmi_debug_shadow.argtypes = [vp, u32, vp, vp, vp, u32, vp]
         _brmi_lib = lib
     return _brmi_lib

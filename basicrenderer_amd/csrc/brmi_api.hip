@@ -180,6 +180,7 @@ static void compute_sizes(brmi_pass* p) {
     w.lateList = take(p->holdEnabled ? (uint64_t)c.maxVisibleClusters * 4 : 16);
     w.wideQueue = take((uint64_t)std::max(1u, p->wideCapacity) * 96);      // WideTri (brmi_raster.hip)
     w.wideAlpha = take(p->tables.hasAlphaTest ? (uint64_t)std::max(1u, p->wideCapacity) * 48 : 16);
+    w.shadowRecords = take((uint64_t)std::max(1u, p->scene.lightCount) * 32 + 32);              // the shading pass's 32 B shadow record per active light (brmi_shadow.h)
     w.total = off;
     p->resNeed[BRMI_RES_WORKSPACE] = w.total;
 }
@@ -320,6 +321,7 @@ int brmi_set_scene(brmi_pass* p, const brmi_scene_buffers* scene) {
     p->scene = *scene; p->haveScene = false; p->setupDone = false;
     p->streaming.on = false;      // (bound to the group table of the scene before: brmi_set_streaming again)
     p->samplerAniso = nullptr;    // (one word per sampler of the scene before: brmi_set_sampler_anisotropy again)
+    p->shadows.on = false; p->shadows.b = brmi_shadow_buffers{};      // (validated against the lights and cameras of the scene before: brmi_set_shadows again)
     const brmi_scene_buffers& sc = p->scene;
     if (!sc.slabs || !sc.perObject || !sc.perMesh || !sc.perMeshInstance || !sc.clodOffsets || !sc.meshMetadata || !sc.lodNodes || !sc.lodGroups ||
         !sc.lodSegments || !sc.groupPageMap || !sc.materials || !sc.openpbrMaterials || !sc.cameras || !sc.cullingCameras || !sc.viewRasterInfo || !sc.perFrame ||
@@ -1187,6 +1189,65 @@ int brmi_debug_ibl(brmi_pass* p, const brmi_environment_buffers* env, uint32_t e
     if (!normals || !albedo || !metallicRoughness || !coat || !emissive || !fuzz || !viewWS || !outDiffuse || !outSpecular) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_debug_ibl: a null pointer");
     if (n == 0u) return BRMI_OK;
     return brmi::launch_debug_ibl(p, environment_struct_of(env), environmentIndex, normals, albedo, metallicRoughness, coat, emissive, fuzz, viewWS, outDiffuse, outSpecular, n, static_cast<hipStream_t>(stream));
+}
+// ---- shadow maps of spot and point lights (brmi_shadow.hip, brmi_shadow.h): every refusal comes before anything of the pass changes
+int brmi_set_shadows(brmi_pass* p, const brmi_shadow_buffers* b) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (!b) { if (p->shadows.on) p->updateSerial++; p->shadows.on = false; p->shadows.b = brmi_shadow_buffers{}; return BRMI_OK; }
+    if (b->structSize != sizeof(brmi_shadow_buffers)) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_shadows: structSize %u, expected %zu", b->structSize, sizeof(brmi_shadow_buffers));
+    if (!p->haveScene) return brmi::fail(p, BRMI_ERR_STATE, "brmi_set_shadows: brmi_set_scene first (the binding is checked against the scene's lights and cameras)");
+    if ((!b->maps && b->mapCount) || (!b->spotCameraIndices && b->spotCount) || (!b->pointCameraIndices && b->pointCount))
+        return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_shadows: a null table with a non-zero count");
+    if (b->pointCount > 0xFFFFFFFFu / 6u) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_shadows: pointCount %u", b->pointCount);
+    // what the host can see: the lights, the descriptors and the two index arrays, read back once
+    std::vector<brmi_light_info> lights; std::vector<brmi_texture_desc> maps; std::vector<uint32_t> spot, point;
+    if (int rc = read_back(p, lights, p->scene.lights, p->scene.lightCount)) return rc;
+    if (int rc = read_back(p, maps, b->maps, b->mapCount)) return rc;
+    if (int rc = read_back(p, spot, b->spotCameraIndices, b->spotCount)) return rc;
+    if (int rc = read_back(p, point, b->pointCameraIndices, (size_t)b->pointCount * 6u)) return rc;
+    for (size_t i = 0; i < maps.size(); i++) {
+        const brmi_texture_desc& d = maps[i];
+        if (d.format != BRMI_TEXTURE_FORMAT_R32_FLOAT) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_shadows: map %zu has format %u, expected BRMI_TEXTURE_FORMAT_R32_FLOAT", i, d.format);
+        if (!d.texels || d.width == 0u || d.height == 0u || d.mipCount != 1u || (reinterpret_cast<uintptr_t>(d.texels) & 3u))
+            return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_shadows: map %zu needs texels (4 B aligned), a size and exactly one level", i);
+    }
+    for (size_t i = 0; i < spot.size(); i++) if (spot[i] >= p->scene.cameraCount) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_shadows: spot view %zu names camera %u of %u", i, spot[i], p->scene.cameraCount);
+    for (size_t i = 0; i < point.size(); i++) if (point[i] >= p->scene.cameraCount) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_shadows: point view %zu names camera %u of %u", i, point[i], p->scene.cameraCount);
+    for (size_t i = 0; i < lights.size(); i++) {
+        const brmi_light_info& l = lights[i];
+        const bool spotL = l.type == BRMI_LIGHT_SPOT, pointL = l.type == BRMI_LIGHT_POINT;
+        if ((!spotL && !pointL) || l.shadowViewInfoIndex == -1 || l.shadowMapIndex == -1) continue;      // unshadowed (a directional light always is)
+        const uint64_t lastMap = (uint64_t)(uint32_t)l.shadowMapIndex + (pointL ? 5u : 0u);
+        if (l.shadowMapIndex < 0 || lastMap >= b->mapCount) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_shadows: light %zu names shadow map %d, the table has %u", i, l.shadowMapIndex, b->mapCount);
+        if (l.shadowViewInfoIndex < 0 || (uint32_t)l.shadowViewInfoIndex >= (spotL ? b->spotCount : b->pointCount))
+            return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_shadows: light %zu names %s view %d, the table has %u", i, spotL ? "spot" : "point", l.shadowViewInfoIndex, spotL ? b->spotCount : b->pointCount);
+        if (pointL) for (uint32_t f = 0; f < 6u; f++) {
+            const brmi_texture_desc& d = maps[(size_t)l.shadowMapIndex + f];
+            if (d.width != d.height || d.width != maps[(size_t)l.shadowMapIndex].width) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_shadows: light %zu: the six faces from map %d on must be square and of one size", i, l.shadowMapIndex);
+        }
+    }
+    p->shadows.b = *b; p->shadows.on = true;
+    p->updateSerial++;       // the frame constants build the per-light shadow records: re-evaluated by the next stage call
+    return BRMI_OK;
+}
+int brmi_shadow_capture(brmi_pass* p, float zNear, float zFar, const brmi_texture_desc* dst, brmi_stream stream) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (!p->setupDone) return brmi::fail(p, BRMI_ERR_STATE, "brmi_shadow_capture: call brmi_setup first");
+    if (!dst || !dst->texels || (reinterpret_cast<uintptr_t>(dst->texels) & 3u)) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_shadow_capture: no destination (texels 4 B aligned)");
+    if (dst->format != BRMI_TEXTURE_FORMAT_R32_FLOAT || dst->mipCount != 1u) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_shadow_capture: the destination must be BRMI_TEXTURE_FORMAT_R32_FLOAT with one level");
+    if (dst->width != p->cfg.width || dst->height != p->cfg.height) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_shadow_capture: the destination is %u x %u, the pass renders %u x %u", dst->width, dst->height, p->cfg.width, p->cfg.height);
+    if (p->stripes.count > 1u || p->bandY0 != 0u || p->bandY1 != p->cfg.height) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_shadow_capture: not with a row band or the interleaved partition (a map is a whole view)");
+    if (!std::isfinite(zNear) || !std::isfinite(zFar) || !(zNear > 0.0f) || !(zFar > zNear)) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_shadow_capture: zNear %g, zFar %g", (double)zNear, (double)zFar);
+    if (!p->res[BRMI_RES_LINEAR_DEPTH]) return brmi::fail(p, BRMI_ERR_STATE, "brmi_shadow_capture: the depth surface is not bound");
+    return brmi::launch_shadow_capture(p, zNear, zFar, *dst, static_cast<hipStream_t>(stream));
+}
+int brmi_debug_shadow(brmi_pass* p, uint32_t lightIndex, const float* positionsWS, const float* normalsWS, float* outShadow, uint32_t n, brmi_stream stream) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (!p->shadows.on) return brmi::fail(p, BRMI_ERR_STATE, "brmi_debug_shadow: no shadow maps bound (brmi_set_shadows)");
+    if (lightIndex >= p->scene.lightCount) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_debug_shadow: light %u of %u", lightIndex, p->scene.lightCount);
+    if (!positionsWS || !normalsWS || !outShadow) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_debug_shadow: a null pointer");
+    if (n == 0u) return BRMI_OK;
+    return brmi::launch_debug_shadow(p, lightIndex, positionsWS, normalsWS, outShadow, n, static_cast<hipStream_t>(stream));
 }
 int brmi_debug_sample_grad(const brmi_scene_buffers* scene, const uint32_t* maxAnisotropy, uint32_t textureIndex, uint32_t samplerIndex, uint32_t uniformBinding, const float* uv, const float* ddx,
                            const float* ddy, float* outRGBA, uint32_t n, brmi_stream stream) {

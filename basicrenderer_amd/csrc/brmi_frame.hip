@@ -13,6 +13,7 @@
 #include "brmi_internal.h"
 #include "brmi_texture.h"
 #include "brmi_shade_math.h"
+#include "brmi_shadow.h"
 
 namespace brmi {
 
@@ -135,7 +136,8 @@ __global__ void __launch_bounds__(256) k_fill_layer_planes(LayerUniform* L, unsi
 // view-space bounding spheres of the active lights, once per frame (testSphereAABB's transform, lightCulling.hlsl:15-21)
 // ... and the shading pass's record of the light (brmi_light.hip, ShadeLightLanes): what getLightParametersForFragment reads, 64 B, indexed
 // (four float4) by the position in the active-light list.  normalize(dirWorldSpace) of a spot light is per light, not per pixel (lighting.hlsli:640).
-BRMI_DEV void job_light_spheres(const brmi_scene_buffers& sc, float4* lightVS, uint32_t* lightMeta, float4* shadeLights, uint32_t i) {
+// ... and, with shadow maps bound (brmi_set_shadows; null without), the light's 32 B shadow record under the same index (brmi_shadow.h)
+BRMI_DEV void job_light_spheres(const brmi_scene_buffers& sc, float4* lightVS, uint32_t* lightMeta, float4* shadeLights, ShadowRecord* shadowRecords, uint32_t i) {
     const brmi_per_frame* pf = sc.perFrame;
     if (i >= pf->numLights) return;
     const m4 view = load_m4(&sc.cameras[pf->mainCameraIndex].view[0][0]);
@@ -145,6 +147,7 @@ BRMI_DEV void job_light_spheres(const brmi_scene_buffers& sc, float4* lightVS, u
     lightVS[i] = make_float4(c.x, c.y, c.z, l->boundingSphere[3]);
     // the clustering's `switch (light.type)` (lightCulling.hlsl:101-116) has cases 0, 1 and 2 and no default: every other type keeps the code 3 = in no cluster
     lightMeta[i] = min(l->type, 3u) | (li << 2);
+    if (shadowRecords) shadowRecords[i] = shadow_record_of(l);
     float4* r = shadeLights + (size_t)i * 4u;
     const f3 dir{l->dirWorldSpace[0], l->dirWorldSpace[1], l->dirWorldSpace[2]};
     if (l->type == BRMI_LIGHT_DIRECTIONAL) r[0] = make_float4(-dir.x, -dir.y, -dir.z, -1.0f);     // lightToFrag; a negative range marks the type
@@ -245,6 +248,7 @@ struct FrameJobs {
     uint4* frameState; uint64_t frameState16;      // brmi_execute: the culling pass's counters + survivor bitmasks, zeroed here (job 7)
     uint32_t firstBlock[8];      // block ranges of the seven jobs
     const brmi_environment_info* environment;      // brmi_set_environment: the record perFrame.activeEnvironmentIndex names (null: no environment bound)
+    ShadowRecord* shadowRecords;                   // brmi_set_shadows: one record per active light (null: no shadow maps bound)
 };
 
 __global__ void __launch_bounds__(64) k_frame_constants(FrameJobs j) {
@@ -253,7 +257,7 @@ __global__ void __launch_bounds__(64) k_frame_constants(FrameJobs j) {
     else if (b < j.firstBlock[2]) job_material_words(j.sc, j.matWords, j.alphaMats, (b - j.firstBlock[1]) * 64u + threadIdx.x);
     else if (b < j.firstBlock[3]) job_material_constants(j.sc, j.matConst, (b - j.firstBlock[2]) * 64u + threadIdx.x);
     else if (b < j.firstBlock[4]) job_shade_tables(j.sc, j.tables, j.W, j.H, j.stripes, j.sliceStart, (b - j.firstBlock[3]) * 64u + threadIdx.x);
-    else if (b < j.firstBlock[5]) job_light_spheres(j.sc, j.lightVS, j.lightMeta, j.shadeLights, (b - j.firstBlock[4]) * 64u + threadIdx.x);
+    else if (b < j.firstBlock[5]) job_light_spheres(j.sc, j.lightVS, j.lightMeta, j.shadeLights, j.shadowRecords, (b - j.firstBlock[4]) * 64u + threadIdx.x);
     else if (b < j.firstBlock[6]) job_shade_material_table(j.sc, j.lutF, j.shadeRows, j.shadeAvgs, j.ggxQuads, (b - j.firstBlock[5]) * 64u + threadIdx.x);
     else if (b < j.firstBlock[7]) { for (uint64_t i = (uint64_t)(b - j.firstBlock[6]) * 64u + threadIdx.x; i < j.frameState16; i += (uint64_t)(j.firstBlock[7] - j.firstBlock[6]) * 64u) j.frameState[i] = make_uint4(0u, 0u, 0u, 0u); }
     else job_layer_uniform(j.sc, j.layer, threadIdx.x);
@@ -286,6 +290,7 @@ int ensure_frame_constants(brmi_pass* p, FrameCtx& ctx, hipStream_t s) {
     for (int k = 0; k < 3; k++) { j.bandPlanes[k] = p->bandPlaneTop[k]; j.bandPlanes[4 + k] = p->bandPlaneBottom[k]; }
     j.bandPlanes[3] = j.bandPlanes[7] = 0.0f;
     j.environment = nullptr;
+    j.shadowRecords = p->shadows.on ? p->wsPtr<ShadowRecord>(p->ws.shadowRecords) : nullptr;
     if (p->env.on) {
         if (p->pfHost.activeEnvironmentIndex >= p->env.b.environmentCount) return fail(p, BRMI_ERR_INVALID, "perFrame.activeEnvironmentIndex (%u) exceeds the environment table (%u)", p->pfHost.activeEnvironmentIndex, p->env.b.environmentCount);
         j.environment = p->env.b.environments + p->pfHost.activeEnvironmentIndex;

@@ -267,7 +267,7 @@ struct Workspace {     // byte offsets into BRMI_RES_WORKSPACE
     uint64_t counters, frontierA, frontierB, buckets, tempVisible, bitmask1, bitmask2, blockDirty, chainDirty, wordPrefix, blockSums,
              instanceBitBase, segPrefix, meshLevelWidth, scanAgg, flatNodes, flatLeaves, instanceWalk, planes, replayNodes, replayBuckets, lightVS, lightMeta, clusterPages, clusterHits, pageTotal, lightHitMasks, binCounts, binRecords, binOverflow, binPlan, binItems, binScratch, clusterSetup, resolveVerts, resolveTris, matWords, shadeTables, lutF, frameConst, objConst, matConst, deferredPixels,
              frameSnapshot, clusterUv, binAlpha, overflowAlpha, resolveUVs, resolveColors, alphaMats, shadeRows, shadeAvgs, ggxQuads, shadeLights, clusterList, listEntries, listRecords, layerUniform,
-             meshletBoxes, pageBoxBase, pageRefs, drawList, heldRecords, lateList, wideQueue, wideAlpha, generalList, bigQueue, bigRuns, frameClearBytes, total;
+             meshletBoxes, pageBoxBase, pageRefs, drawList, heldRecords, lateList, wideQueue, wideAlpha, generalList, bigQueue, bigRuns, shadowRecords, frameClearBytes, total;
 };
 
 // One frame being issued and nothing else.  Made by whoever starts the frame -- brmi_execute_split, which asks for the fused forms below, or a public stage entry
@@ -398,6 +398,8 @@ struct brmi_pass {
     struct { bool on = false; brmi_environment_buffers b{}; } env;      // brmi_set_environment (kept by brmi_set_scene: nothing of it depends on the scene)
     struct { bool on = false; brmi_gtao_buffers b{}; brmi_gtao_layout layout{}; } gtao;      // brmi_set_gtao (kept by brmi_set_scene: sized by the frame alone)
     struct { bool on = false; brmi_display_buffers b{}; brmi_display_layout layout{}; } display;      // brmi_set_display (kept by brmi_set_scene: sized by the frame alone)
+    // brmi_set_shadows (forgotten by brmi_set_scene: validated against the scene's lights and cameras)
+    struct { bool on = false; brmi_shadow_buffers b{}; } shadows;
     uint32_t frameIndexHost = 0;                 // brmi_frame_update::frameIndex of the last brmi_update (the GTAO noise's temporal index)
     const uint32_t* samplerAniso = nullptr;      // brmi_set_sampler_anisotropy: device words, one per sampler of the scene (cleared by brmi_set_scene)
     brmi_camera camHost{};
@@ -468,6 +470,9 @@ int launch_env_convert(const brmi_texture_desc* equirect, const brmi_texture_des
 int launch_env_project_sh(const brmi_texture_desc* cubemaps, uint32_t cubemapCount, brmi_environment_info* env, uint32_t size, hipStream_t s);
 int launch_env_prefilter(const brmi_texture_desc* source, const brmi_texture_desc* prefiltered, uint32_t size, uint32_t levels, hipStream_t s);
 int launch_debug_env_lookup(const brmi_texture_desc* cubemaps, uint32_t cubemapCount, uint32_t cubemap, const float* dirs, const float* lods, float* outRGBA, uint32_t n, hipStream_t s);
+// brmi_shadow.hip (the entry points have checked their arguments)
+int launch_shadow_capture(brmi_pass* p, float zNear, float zFar, const brmi_texture_desc& dst, hipStream_t s);
+int launch_debug_shadow(brmi_pass* p, uint32_t lightIndex, const float* positionsWS, const float* normalsWS, float* outShadow, uint32_t n, hipStream_t s);
 // brmi_texmips.hip (the entry points have checked the descriptor: a host copy, `texels` a device pointer)
 int launch_texmips_plain(const brmi_texture_desc& texture, const float* srgbToLinear, uint32_t* counter, hipStream_t s);
 int launch_texmips_alpha(const brmi_texture_desc& texture, const float* srgbToLinear, uint32_t* stats, float* scales, hipStream_t s);

@@ -52,9 +52,11 @@ __global__ void __launch_bounds__(256) k_lc_fill(ClusterArgs a) { lc_fill_block(
 #ifndef BRMI_SHADE_WAVES_ALONE
 #define BRMI_SHADE_WAVES_ALONE 5
 #endif
+// (The value is a TAG in the kernel names as much as a budget: k_shade_ibl*, and every k_shade*_shadow, compile their `<0, 5>` instantiation for FOUR waves per
+// SIMD -- see their attributes below -- and keep the 5 in the name only to tell the stand-alone variant from the one that shares the chip.)
 static_assert(BRMI_SHADE_WAVES_ALONE != BRMI_SHADE_WAVES, "the two variants of k_shade<0> are told apart by their waves per SIMD");
 // (the body of k_shade and k_shade_ibl: IBL = the environment term, shade_pixel)
-template <int MODE, int WAVES, bool IBL, bool GTAO = false>
+template <int MODE, int WAVES, bool IBL, bool GTAO = false, bool SHADOWS = false>
 BRMI_DEV void shade_kernel(const ShadeArgs& a) {
     constexpr bool ALONE = WAVES == BRMI_SHADE_WAVES_ALONE;
     // The variant that shares the chip holds 136 registers per wave ON PURPOSE (round 5: the arithmetic needs 123): three of its waves then leave a SIMD
@@ -107,7 +109,7 @@ BRMI_DEV void shade_kernel(const ShadeArgs& a) {
             const uint64_t tileBase = (uint64_t)(firstTile + t) << 6;
             uint32_t ls = lane;
             if (ALONE) asm volatile("" : "+v"(ls));
-            const uint32_t cls = shade_pixel<0, ALONE ? BRMI_SHADE_STASH_ALONE : 0, IBL, GTAO>(a, k, sliceStart, unormT, camK, cur, ok, tileBase, ls);
+            const uint32_t cls = shade_pixel<0, ALONE ? BRMI_SHADE_STASH_ALONE : 0, IBL, GTAO, SHADOWS>(a, k, sliceStart, unormT, camK, cur, ok, tileBase, ls);
             shade_defer(a, t, cls, ls);
             if (ALONE) nxt = fetch(nt, ntx, nty, nok);      // (the stand-alone variant: the next tile's words requested behind this tile's shading, ~14 registers less in it)
             cur = nxt; ok = nok; t = nt; tx = ntx; ty = nty;
@@ -141,7 +143,7 @@ BRMI_DEV void shade_kernel(const ShadeArgs& a) {
                 px = (tile % a.tilesX) * 8u + (within >> 3); py = (tile / a.tilesX) * 8u + (within & 7u);
                 raw = load_raw_pixel(a, i, px, py);
             }
-            shade_pixel<MODE, 0, IBL, GTAO>(a, k, sliceStart, unormT, camK, raw, ok, i & ~63ull, (uint32_t)(i & 63ull));
+            shade_pixel<MODE, 0, IBL, GTAO, SHADOWS>(a, k, sliceStart, unormT, camK, raw, ok, i & ~63ull, (uint32_t)(i & 63ull));
         }
     }
 }
@@ -158,6 +160,18 @@ k_shade_ibl(ShadeArgs a) { shade_kernel<MODE, WAVES, true>(a); }
 template <int MODE, int WAVES = BRMI_SHADE_WAVES>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE != 0 ? 1 : (WAVES == BRMI_SHADE_WAVES_ALONE ? 4 : WAVES), 8)))
 k_shade_ibl_ao(ShadeArgs a) { shade_kernel<MODE, WAVES, true, true>(a); }
+// ... and with shadow maps bound (brmi_set_shadows): each of the three with the shadow test in its light loop, once more under names of their own -- a pass
+// without the binding launches the kernels above, register for register.  The stand-alone plain variant is compiled for four waves per SIMD in all three:
+// the lookup's temporaries do not fit the five-wave budget (profiles/shadow_resources.md).
+template <int MODE, int WAVES = BRMI_SHADE_WAVES>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE != 0 ? 1 : (WAVES == BRMI_SHADE_WAVES_ALONE ? 4 : WAVES), 8)))
+k_shade_shadow(ShadeArgs a) { shade_kernel<MODE, WAVES, false, false, true>(a); }
+template <int MODE, int WAVES = BRMI_SHADE_WAVES>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE != 0 ? 1 : (WAVES == BRMI_SHADE_WAVES_ALONE ? 4 : WAVES), 8)))
+k_shade_ibl_shadow(ShadeArgs a) { shade_kernel<MODE, WAVES, true, false, true>(a); }
+template <int MODE, int WAVES = BRMI_SHADE_WAVES>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE != 0 ? 1 : (WAVES == BRMI_SHADE_WAVES_ALONE ? 4 : WAVES), 8)))
+k_shade_ibl_ao_shadow(ShadeArgs a) { shade_kernel<MODE, WAVES, true, true, true>(a); }
 
 __global__ void __launch_bounds__(256) k_expand_luts(const uint16_t* odE, const uint16_t* odAvg, const uint16_t* imE, const uint16_t* imAvg, float* out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -226,6 +240,7 @@ ShadeArgs shade_args_of(brmi_pass* p) {
     a.stripeCapacity = p->deferredStripeCapacity;
     a.envSH = p->wsPtr<FrameSnapshot>(p->ws.frameSnapshot)->envSH; a.envCubemaps = p->env.b.cubemaps; a.envCubemapCount = p->env.b.cubemapCount; a.envSpecular = p->env.b.specularIBL ? 1u : 0u;
     a.aoTerm = p->gtao.on ? static_cast<const uint8_t*>(p->gtao.b.aoTerm) : nullptr;
+    a.shadow = shadow_bind_of(p);
     return a;
 }
 
@@ -258,6 +273,20 @@ static int launch_shade_range(brmi_pass* p, bool sharesChip, hipStream_t s, uint
     // and, with another frame's geometry half in flight beside it, slots come free twice as often for that half's high-priority launches
     // (Bistro 4K, two frames in flight: 0.436 -> 0.413 ms per frame; 16384: 0.425, 2048: 0.49)
     // a bound environment (brmi_set_environment) selects the k_shade_ibl instantiations; without one the launches are the ones they always were
+    if (p->shadows.on) {      // brmi_set_shadows: the same choice among the three families, each with the shadow test in its light loop
+#define BRMI_LAUNCH_SHADOWED(K) do { \
+        if (sharesChip) hipLaunchKernelGGL((K<0, BRMI_SHADE_WAVES>), dim3(std::max(256u, p->shadeGridShared / share)), dim3(256), 0, s, a); \
+        else hipLaunchKernelGGL((K<0, BRMI_SHADE_WAVES_ALONE>), dim3(std::max(256u, 8192u / share)), dim3(256), 0, s, a); \
+        if (p->tables.hasCoat) hipLaunchKernelGGL(K<1>, dim3(512), dim3(256), 0, s, a); \
+        if (p->tables.hasFuzz) hipLaunchKernelGGL(K<2>, dim3(512), dim3(256), 0, s, a); \
+        if (p->tables.hasCoat && p->tables.hasFuzz) hipLaunchKernelGGL(K<3>, dim3(512), dim3(256), 0, s, a); } while (0)
+        if (p->env.on && p->gtao.on) BRMI_LAUNCH_SHADOWED(k_shade_ibl_ao_shadow);
+        else if (p->env.on) BRMI_LAUNCH_SHADOWED(k_shade_ibl_shadow);
+        else BRMI_LAUNCH_SHADOWED(k_shade_shadow);
+#undef BRMI_LAUNCH_SHADOWED
+        BRMI_LAUNCH_CHECK(p, "k_shade_shadow");
+        return BRMI_OK;
+    }
     if (p->env.on && p->gtao.on) {      // (without an environment nothing reads the term: the k_shade launches below)
         if (sharesChip) hipLaunchKernelGGL((k_shade_ibl_ao<0, BRMI_SHADE_WAVES>), dim3(std::max(256u, p->shadeGridShared / share)), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((k_shade_ibl_ao<0, BRMI_SHADE_WAVES_ALONE>), dim3(std::max(256u, 8192u / share)), dim3(256), 0, s, a);

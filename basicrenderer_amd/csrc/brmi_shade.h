@@ -7,6 +7,7 @@
 #include "brmi_internal.h"
 #include "brmi_shade_math.h"
 #include "brmi_texture.h"
+#include "brmi_shadow.h"
 
 namespace brmi {
 
@@ -181,6 +182,8 @@ struct ShadeArgs {
     const float* envSH; const brmi_texture_desc* envCubemaps; uint32_t envCubemapCount, envSpecular;
     // XeGTAO's final term (brmi_set_gtao), one visibility code per pixel in the surfaces' layout; read by the k_shade_ibl_ao instantiations alone
     const uint8_t* aoTerm;
+    // shadow maps of spot and point lights (brmi_set_shadows), read by the k_shade*_shadow instantiations alone
+    ShadowBind shadow;
 };
 
 BRMI_DEV float half_at(unsigned long long v, int k) { return f16_bits_to_f32((uint32_t)(v >> (16 * k)) & 0xFFFFu); }
@@ -538,7 +541,11 @@ BRMI_DEV void build_fragment(const ShadeArgs& a, const ShadeFrame& k, const floa
 // GTAO (with IBL only: punctual lights never read the value, lighting.hlsli:212, :414): the environment term's visibility is min(albedo.a, aoTerm / 255).  Both are
 // codes decoded by one table, so the minimum of the codes is the code of the minimum.  A template parameter, not a null test on the pointer: the instantiations
 // without it are the kernels they were, register for register.
-template <int MODE, int STASH = 0, bool IBL = false, bool GTAO = false>      // STASH: floats of the metal lobe's inputs parked in LDS (0, 6 or 9)
+// SHADOWS (brmi_set_shadows): a spot or point light whose shadow record says so is tested with calculateSpotShadow / calculatePointShadow before its
+// BRDF; the result is exactly 0 or 1, so a shadowed light is skipped ((1 - 1) * finite = 0, a +0 the sum cannot carry) and a lit one is evaluated as ever.  The
+// 64 B light record is full: the light's index comes from the cluster's list entries (the list position when not clustered) and names a 32 B shadow record --
+// both wave-uniform scalar loads, requested with the light record.  Again instantiations of their own.
+template <int MODE, int STASH = 0, bool IBL = false, bool GTAO = false, bool SHADOWS = false>      // STASH: floats of the metal lobe's inputs parked in LDS (0, 6 or 9)
 BRMI_DEV uint32_t shade_pixel(const ShadeArgs& a, const ShadeFrame& k, const float* sliceStart, const float* unorm8, const float4* camK, const RawPixel& raw, bool live, uint64_t tileBase, uint32_t within) {
     const Luts& L = k.L;
     const uint32_t gx = k.gx, gy = k.gy, gz = k.gz, nearSlices = k.nearSlices;
@@ -649,6 +656,12 @@ BRMI_DEV uint32_t shade_pixel(const ShadeArgs& a, const ShadeFrame& k, const flo
                 const f32x16 w = *reinterpret_cast<const __attribute__((address_space(4))) f32x16*>(kconst(recBase + (size_t)q * 4u));
                 const ShadeLightRecord lr{{w[0], w[1], w[2], w[3]}, {w[4], w[5], w[6], w[7]}, {w[8], w[9], w[10], w[11]}, {w[12], w[13], w[14], w[15]}};
                 const f3 lp{lr.r0[0], lr.r0[1], lr.r0[2]};
+                typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
+                u32x8 sw{};
+                if (SHADOWS) {
+                    const uint32_t li = a.clustered ? kconst(a.listEntries)[listBase + q] : q;
+                    sw = *reinterpret_cast<const __attribute__((address_space(4))) u32x8*>(kconst(a.shadow.records + li));
+                }
                 f3 lightToFrag; float att = 1.0f, spot = 1.0f;
                 if (lr.r0[3] < 0.0f) lightToFrag = lp;           // directional
                 else {
@@ -681,6 +694,11 @@ BRMI_DEV uint32_t shade_pixel(const ShadeArgs& a, const ShadeFrame& k, const flo
                     const float cc = dot3(sd, normalize3_q(-coneDir));
                     if (!(cc > outer)) continue;
                     if (cc < inner) { const float t = satq((cc - outer) / (inner - outer)); spot = t * t * (3.0f - 2.0f * t); }
+                }
+                if (SHADOWS && sw[0] != SHADOW_NONE) {      // (directional lights carry SHADOW_NONE: the VSM branch is not built)
+                    // the decision takes posWS, the normal and the light's position as they are: none of them depends on FAST
+                    const ShadowRecord sr{sw[0], sw[1], sw[2], as_f32(sw[3]), as_f32(sw[4]), {as_f32(sw[5]), as_f32(sw[6]), as_f32(sw[7])}};
+                    if (light_shadow(a.shadow, sr, lp, posWS, f.normalWS) != 0.0f) continue;
                 }
                 const f3 hv = lightToFrag + f.viewWS;
                 const f3 h = FAST ? normalize3_fast(hv) : normalize3_q(hv);

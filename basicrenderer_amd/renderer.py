@@ -96,6 +96,8 @@ class VisibilityRenderer:
             self.res[rid] = t
             binds[i].id, binds[i].ptr, binds[i].bytes = rid, t.data_ptr(), t.numel()
         self.stream = torch.cuda.current_stream(self.device)
+        self._binds = binds
+        self._shadows = None         # set_shadows' maps, index tables and light-view passes
         self._check(self.lib.brmi_setup(self._h, binds, len(self.descs), self._s()), "brmi_setup")
         self.update()
 
@@ -580,6 +582,121 @@ class VisibilityRenderer:
         d["scratch"][int(lay.histogramOffset): int(lay.histogramOffset) + 1024].zero_()
         d["scratch"][int(lay.adaptedLuminanceOffset): int(lay.adaptedLuminanceOffset) + 4].zero_()
 
+    # -- shadow maps of spot and point lights (brmi_set_shadows) ------------------------------------
+    def set_shadows(self, lights, resolution=1024, point_resolution=512):
+        """Shadows from the next frame on for `lights` (indices into the scene's light buffer; spot and point lights only), or None for off -- exactly the
+        frames of a pass that never called this.  Builds one light camera per spot light and six 90 degree cameras per point light the way the reference's
+        light manager does (shadows.light_views), appends them to this pass's camera buffer, fills the lights' shadowViewInfoIndex / shadowMapIndex /
+        shadowSamplerIndex, allocates the R32F maps and owns one light-view pass per resolution.  The maps are rendered by render_shadow_maps(), not by execute()."""
+        from . import shadows as sh
+        torch = self.torch
+        if lights is not None and getattr(self, "_streaming", None) is not None:
+            raise BrmiError("set_shadows: call it before set_streaming (the grown camera buffer is a new scene binding, which forgets the streaming buffers)")
+        if self._shadows is not None:
+            torch.cuda.synchronize(self.device)
+            self._check(self.lib.brmi_set_shadows(self._h, None), "brmi_set_shadows")
+            for r in self._shadows["passes"].values():
+                r.close()
+            self._shadows = None
+        rec = self.device_arrays["lights"].cpu().numpy().view(sh.LIGHT_DTYPE).copy()
+        for k in ("shadowViewInfoIndex", "shadowMapIndex", "shadowSamplerIndex"):
+            rec[k] = -1
+        if lights is None:
+            self.device_arrays["lights"].copy_(torch.from_numpy(rec.view(np.uint8)).to(self.device))
+            self.update(self._frame_index)
+            return
+        main_count = getattr(self, "_main_camera_count", None) or int(self.sb.cameraCount)
+        self._main_camera_count = main_count
+        cams = [self.device_arrays["cameras"].cpu().numpy()[: main_count * sh.CAMERA_BYTES]]
+        views, descs, spot_idx, point_idx, keep = [], [], [], [], []
+        for li in lights:
+            l = rec[int(li)]
+            if int(l["type"]) not in (sh.LIGHT_POINT, sh.LIGHT_SPOT):
+                raise BrmiError(f"set_shadows: light {li} is neither a spot nor a point light (directional shadows are not built)")
+            spot = int(l["type"]) == sh.LIGHT_SPOT
+            res = int(resolution if spot else point_resolution)
+            l["shadowMapIndex"], l["shadowSamplerIndex"] = len(descs), 0
+            l["shadowViewInfoIndex"] = len(spot_idx) if spot else len(point_idx) // 6
+            for cam, cull in sh.light_views(l, res):
+                index = main_count + len(views)
+                (spot_idx if spot else point_idx).append(index)
+                t = torch.zeros((res, res), dtype=torch.float32, device=self.device)
+                d = capi.TextureDesc()
+                d.texels, d.width, d.height, d.mipCount, d.format = t.data_ptr(), res, res, 1, capi.TEXTURE_FORMAT_R32_FLOAT
+                views.append(dict(light=int(li), camera=cam, culling=cull, res=res, map=t, desc=d, near=float(l["nearPlane"]), far=float(l["farPlane"])))
+                descs.append(d)
+                cams.append(cam)
+
+        def up(a):
+            t = torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(self.device)
+            keep.append(t)
+            return t
+        # the grown camera buffer is a new scene binding: brmi_set_scene and brmi_setup again with the resources this pass already owns
+        camera_t = up(np.concatenate(cams))
+        self.device_arrays["cameras"] = camera_t
+        self.device_arrays["lights"].copy_(torch.from_numpy(rec.view(np.uint8)).to(self.device))
+        self.sb.cameras, self.sb.cameraCount = camera_t.data_ptr(), main_count + len(views)
+        torch.cuda.synchronize(self.device)
+        self._check(self.lib.brmi_set_scene(self._h, C.byref(self.sb)), "brmi_set_scene")
+        self._check(self.lib.brmi_setup(self._h, self._binds, len(self.descs), self._s()), "brmi_setup")
+        if self._anisotropy is not None:      # brmi_set_scene forgets the per-sampler table; the samplers are the ones they were
+            self._check(self.lib.brmi_set_sampler_anisotropy(self._h, self._anisotropy.data_ptr(), capi.u32(int(self.sb.samplerCount))), "brmi_set_sampler_anisotropy")
+        b = capi.ShadowBuffers()
+        b.structSize = C.sizeof(capi.ShadowBuffers)
+        desc_bytes = b"".join(bytes(d) for d in descs) or bytes(96)
+        b.maps, b.mapCount = up(np.frombuffer(desc_bytes, dtype=np.uint8)).data_ptr(), len(descs)
+        b.spotCameraIndices, b.spotCount = up(np.array(spot_idx + [0], dtype=np.uint32)).data_ptr(), len(spot_idx)
+        b.pointCameraIndices, b.pointCount = up(np.array(point_idx + [0], dtype=np.uint32)).data_ptr(), len(point_idx) // 6
+        self.update(self._frame_index)
+        self._check(self.lib.brmi_set_shadows(self._h, C.byref(b)), "brmi_set_shadows")
+        self._shadows = dict(buffers=b, keep=keep, views=views, passes={}, lights=rec)
+
+    def _light_pass(self, res):
+        """This pass's light-view pass of `res` x `res` pixels: the scene's geometry (the device buffers are shared) behind one camera of its own."""
+        sd = self._shadows
+        if res not in sd["passes"]:
+            v = next(v for v in sd["views"] if v["res"] == res)
+            view_scene = self.scene.light_view(v["camera"], v["culling"], res, share=(self.sb, self.device_arrays))
+            sd["passes"][res] = VisibilityRenderer(view_scene, device=self.device, max_clusters=int(self.cfg.maxVisibleClusters))
+        return sd["passes"][res]
+
+    def render_shadow_maps(self):
+        """Renders every map of set_shadows: per view the camera, the geometry stages through their entry points (clear, cull, raster, depth copy), then
+        brmi_shadow_capture.  execute() never does this: a static scene renders its maps once."""
+        if self._shadows is None:
+            raise BrmiError("render_shadow_maps: set_shadows first")
+        for k in range(len(self._shadows["views"])):
+            self.render_shadow_view(k)
+        self.torch.cuda.synchronize(self.device)
+
+    def render_shadow_view(self, index):
+        """One map of set_shadows (descriptor order), issued on the current stream and not waited for."""
+        torch, v = self.torch, self._shadows["views"][index]
+        r = self._light_pass(v["res"])
+        r.device_arrays["cameras"].copy_(torch.from_numpy(v["camera"]).to(self.device))
+        r.device_arrays["cullingCameras"].copy_(torch.from_numpy(v["culling"]).to(self.device))
+        r._cam_bytes = v["camera"]
+        r.update(self._frame_index)
+        r.stage("clear_visibility"); r.stage("cull", 1); r.stage("raster", 1); r.stage("depth_copy")
+        r._check(self.lib.brmi_shadow_capture(r._h, capi.f32(v["near"]), capi.f32(v["far"]), C.byref(v["desc"]), r._s()), "brmi_shadow_capture")
+
+    def shadow_maps(self):
+        """The maps as (res, res) float32 arrays, in descriptor order (a point light's six faces +X -X +Y -Y +Z -Z in a row)."""
+        if self._shadows is None:
+            raise BrmiError("shadow_maps: set_shadows first")
+        self.torch.cuda.synchronize(self.device)
+        return [v["map"].cpu().numpy() for v in self._shadows["views"]]
+
+    def debug_shadow(self, light, positions, normals):
+        """brmi_debug_shadow: the shadow function of light `light` for made-up receivers ((n, 3) world positions and normals) -> (n,) float32 of 0 / 1."""
+        torch = self.torch
+        pos = torch.from_numpy(np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)).to(self.device)
+        nrm = torch.from_numpy(np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)).to(self.device)
+        out = torch.full((max(1, pos.shape[0]),), -1.0, dtype=torch.float32, device=self.device)
+        self._check(self.lib.brmi_debug_shadow(self._h, capi.u32(int(light)), pos.data_ptr(), nrm.data_ptr(), out.data_ptr(), capi.u32(pos.shape[0]), self._s()), "brmi_debug_shadow")
+        torch.cuda.synchronize(self.device)
+        return out.cpu().numpy()[: pos.shape[0]]
+
     # -- debug views (brmi_set_debug_view, perFrame.outputType) ------------------------------------
     def set_debug_view(self, mode, fill=0, check=True):
         """The debug view of the frames from the next update() on: a perFrame.outputType number or the reference's name without the OUTPUT_ prefix
@@ -671,6 +788,10 @@ class VisibilityRenderer:
             self._environment = None
             self._gtao = None
             self._display = None
+            if getattr(self, "_shadows", None) is not None:
+                for r in self._shadows["passes"].values():
+                    r.close()
+            self._shadows = None
             self._scene_keep = []
             self.device_arrays = {}
             if hasattr(self.scene, "device_arrays"):

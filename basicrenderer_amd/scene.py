@@ -212,6 +212,26 @@ class Scene:
     def per_frame_host(self):
         return self.arrays["perFrame"]
 
+    def light_view(self, camera, culling_camera, resolution, share=None):
+        """This scene's geometry behind ONE other camera at resolution x resolution pixels (a light's view, shadows.light_views): a shallow copy whose
+        cameras, cullingCameras, viewRasterInfo and perFrame are its own.  share = (SceneBuffers, device_arrays) of a pass that has uploaded the scene:
+        device_buffers() then uploads those four arrays alone and takes every other pointer from there."""
+        import copy
+        v = copy.copy(self)
+        v.arrays, v.counts, v._keep, v.pending_chains = dict(self.arrays), dict(self.counts), [], []
+        v.width = v.height = int(resolution)
+        v.arrays["cameras"], v.arrays["cullingCameras"] = np.array(camera, dtype=np.uint8, copy=True), np.array(culling_camera, dtype=np.uint8, copy=True)
+        v.counts["cameras"] = 1
+        ri = self.arrays["viewRasterInfo"][:48].copy()
+        ri.view(np.uint32)[3:7] = [0, 0, resolution, resolution]
+        v.arrays["viewRasterInfo"] = ri
+        pf = self.arrays["perFrame"].copy()
+        pf.view(np.uint32)[8] = 0                      # mainCameraIndex
+        pf.view(np.uint32)[13:15] = resolution       # screenResX, screenResY
+        v.arrays["perFrame"] = pf
+        v._share = share
+        return v
+
     # -- device ----------------------------------------------------------------------------------
     def device_buffers(self, device="cuda"):
         """Upload every array to HBM; returns (SceneBuffers with device pointers, list of tensors to keep alive)."""
@@ -226,6 +246,17 @@ class Scene:
             keep.append(t)
             return t.data_ptr()
 
+        if getattr(self, "_share", None) is not None:      # light_view(share=...): the geometry is in HBM already
+            shared_sb, shared_arrays = self._share
+            C.memmove(C.byref(sb), C.byref(shared_sb), C.sizeof(capi.SceneBuffers))
+            self.device_arrays = dict(shared_arrays)
+            for field, arr, cnt in _FIELD_MAP:
+                if arr in ("cameras", "cullingCameras", "viewRasterInfo", "perFrame"):
+                    setattr(sb, field, up(self.arrays[arr]))
+                    self.device_arrays[arr] = keep[-1]
+                    if cnt:
+                        setattr(sb, cnt, self.counts[arr])
+            return sb, keep
         ptrs = np.zeros(len(self.slabs), dtype=np.uint64)
         for i, s in enumerate(self.slabs):
             if s is not None:

@@ -2,7 +2,7 @@
 """Render a Wavefront OBJ or a glTF 2.0 file (.gltf / .glb) through the whole path on an MI355X and write the lit frame as a PNG
 (Reinhard + sRGB), or -- with --tonemap -- the RGBA8 picture of the library's display chain (auto-exposure, bloom, tone mapping).
 
-    python examples/render_obj.py model.obj|scene.glb out.png [--size 1920x1080] [--lights 32] [--features 0] [--environment sky] [--gtao] [--view NAME]
+    python examples/render_obj.py model.obj|scene.glb out.png [--size 1920x1080] [--lights 32] [--features 0] [--environment sky] [--gtao] [--shadows] [--view NAME]
                                   [--tonemap reinhard|neutral|aces|lpm|none] [--bloom] [--exposure-frames 8]
 
 --view NAME writes a debug view of the frame instead (perFrame.outputType: normal, albedo, metallic, roughness, emissive, ao, depth, meshlets,
@@ -43,6 +43,8 @@ def main():
     ap.add_argument("--tonemap", default=None, choices=["reinhard", "neutral", "aces", "lpm", "none"], help="write the RGBA8 of the library's display chain with this curve (default: off, the file as before)")
     ap.add_argument("--bloom", action="store_true", help="with --tonemap: the bloom pyramid blended into the frame (both sides of the frame at least 32 pixels)")
     ap.add_argument("--exposure-frames", type=int, default=8, metavar="N", help="with --tonemap: render N frames, the last N - 2 with time coefficient 1, so the auto-exposure has settled")
+    ap.add_argument("--shadows", action="store_true", help="shadow maps for every spot and point light of the scene (rendered once, from each light's own views)")
+    ap.add_argument("--shadow-size", type=int, default=1024, metavar="N", help="with --shadows: a spot map is N x N, a cube face N/2 x N/2")
     ap.add_argument("--procedural-materials", action="store_true", help="a glTF file's own materials and textures are used by default; this keeps the procedural stand-ins (--features)")
     a = ap.parse_args()
     from basicrenderer_amd import Scene
@@ -70,6 +72,12 @@ def main():
         r.set_environment(Environment.from_equirect(read_hdr(a.environment)), skybox=a.skybox)
     if a.gtao:
         r.set_gtao(a.gtao)
+    if a.shadows:
+        from basicrenderer_amd import shadows
+        kinds = sc.arrays["lights"].view(shadows.LIGHT_DTYPE)["type"]
+        casters = [int(i) for i in np.flatnonzero((kinds == shadows.LIGHT_SPOT) | (kinds == shadows.LIGHT_POINT))]
+        r.set_shadows(casters, resolution=a.shadow_size, point_resolution=max(32, a.shadow_size // 2))
+        r.render_shadow_maps()      # a still scene: once
     if a.view:
         r.set_debug_view(a.view)
     if a.bloom and not a.tonemap:

@@ -612,6 +612,42 @@ int brmi_debug_ibl(brmi_pass* pass, const brmi_environment_buffers* env, uint32_
 int brmi_debug_env_lookup(const brmi_texture_desc* cubemaps, uint32_t cubemapCount, uint32_t cubemapIndex, const float* directions, const float* lods,
                           float* outRGBA, uint32_t n, brmi_stream stream);
 
+/* ---- shadow maps of spot and point lights --------------------------------------------------------------------------------------------------
+ * The `GetRootEnableShadows()` block of the light loop (BR/shaders/Include/lighting.hlsli:536-560) for its point and spot branches: calculatePointShadow and
+ * calculateSpotShadow of BR/shaders/Include/shadows.hlsli, restated as written.  The directional branch (virtual shadow maps) is not built: a directional light
+ * is never shadowed, whatever its fields say.
+ *   maps                device array of brmi_texture_desc, BRMI_TEXTURE_FORMAT_R32_FLOAT, one level each.  A spot light's shadowMapIndex names one descriptor; a
+ *                       point light's names the first of six consecutive square faces in the order +X -X +Y -Y +Z -Z.
+ *   spotCameraIndices   Builtin::Light::SpotLightMatrixBuffer: entry light.shadowViewInfoIndex is the light view's index in brmi_scene_buffers::cameras.
+ *   pointCameraIndices  Builtin::Light::PointLightCubemapBuffer: entries light.shadowViewInfoIndex * 6 + face, six per light (pointCount counts lights).
+ * The cameras named here are read from the CALLER's camera buffer (not from the frame's snapshot of the main camera): they stay as they are while a frame
+ * that reads them is in flight, like the lights and the maps.
+ * A light whose shadowViewInfoIndex or shadowMapIndex is -1 is unshadowed.  The lookup is a plain bilinear fetch of level 0: fp32 weights, a tap outside a
+ * spot map reads the border value 1.0; a cube takes the face, the texel addresses and the edge rule of the environment cube lookup.
+ * brmi_set_shadows reads the lights, the descriptors and the index arrays back once and refuses with BRMI_ERR_INVALID: a wrong structSize, a null table with a
+ * non-zero count, a shadowed spot / point light whose shadowMapIndex (+ 5 for a point light) is outside `maps` or whose shadowViewInfoIndex is outside its
+ * index array, a spot or point view index >= cameraCount, and a descriptor whose format is not R32_FLOAT (or that has no texels, no size or more than one level).
+ * NULL unbinds and gives exactly the frames -- kernels, bytes -- of a pass that never called it.  brmi_set_scene forgets the binding (it is validated against
+ * the scene's lights and cameras). */
+typedef struct brmi_shadow_buffers {
+    uint32_t structSize;                        /* sizeof(brmi_shadow_buffers) */
+    uint32_t reserved;
+    const brmi_texture_desc* maps;              uint32_t mapCount;    uint32_t reserved0;
+    const uint32_t*          spotCameraIndices; uint32_t spotCount;   uint32_t reserved1;
+    const uint32_t*          pointCameraIndices; uint32_t pointCount; uint32_t reserved2;
+} brmi_shadow_buffers;                          /* 56 B */
+int brmi_set_shadows(brmi_pass* pass, const brmi_shadow_buffers* buffers_or_NULL);
+/* A light view's depth as the shadow map the shader samples.  `lightPass` has rendered the view (clear, cull, raster, depth copy).  brmi_depth_copy MUST have
+ * run: the kernel reads the depth surface alone and takes the "empty" word that stage writes for an empty visibility key as background.  It reads the pass's tiled
+ * linear depth (BRMI_RES_LINEAR_DEPTH) and writes dst->texels (device, R32_FLOAT, row-major, dst->width x dst->height = the pass's frame; `dst` is a HOST struct):
+ * 1.0f for a pixel without geometry, else d = zFar * (z - zNear) / (z * (zFar - zNear)) in fp32 in that order -- what the reference's light projection
+ * (XMMatrixPerspectiveFovRH(.., nearPlane, farPlane)) leaves in its depth target, the inverse of the shader's unprojectDepth. */
+int brmi_shadow_capture(brmi_pass* lightPass, float zNear, float zFar, const brmi_texture_desc* dst, brmi_stream stream);
+/* The shadow function of light `lightIndex` (an index into brmi_scene_buffers::lights) alone, for n made-up receivers: positionsWS / normalsWS n float3 each,
+ * outShadow n floats (1 = shadowed, 0 = lit or unshadowed light), all device pointers.  The device function is the one the shading kernels call.  Needs a
+ * binding (BRMI_ERR_STATE without one). */
+int brmi_debug_shadow(brmi_pass* pass, uint32_t lightIndex, const float* positionsWS, const float* normalsWS, float* outShadow, uint32_t n, brmi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

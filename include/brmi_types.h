@@ -407,6 +407,9 @@ typedef struct brmi_openpbr_material_info {
 /* Four IEEE halves per texel (8 B; `texels` 8-byte aligned; mipOffset stays in TEXELS): the reference's environment cube, R16G16B16A16_Float.  Only the environment
  * build (brmi_env_*) and the skybox stage (brmi_skybox) honour it; the material sampler, the alpha test and the shading pass's prefiltered cube read RGBA8. */
 #define BRMI_TEXTURE_FORMAT_RGBA16_FLOAT      2u
+/* One IEEE fp32 per texel, row-major (4 B; mipOffset in TEXELS): a shadow map, the reference's R32_Float depth target.  Only the shadow entry points
+ * (brmi_set_shadows, brmi_shadow_capture, brmi_debug_shadow) honour it. */
+#define BRMI_TEXTURE_FORMAT_R32_FLOAT         3u
 #define BRMI_TEXTURE_MAX_MIPS                 16u
 typedef struct brmi_texture_desc {
     const uint8_t* texels;                  /* device pointer, 4-byte aligned (scene generator output: byte offset into BRMI_ARR_TEXELS) */
