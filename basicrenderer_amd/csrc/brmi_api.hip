@@ -1120,6 +1120,25 @@ int brmi_debug_read_held(brmi_pass* p, uint32_t* held, uint32_t heldCapacity, ui
     return BRMI_OK;
 }
 
+int brmi_debug_read_draw_list(brmi_pass* p, uint32_t* draw, uint32_t drawCapacity, uint32_t* drawCount, uint32_t* heldBoxes, uint32_t heldCapacity, uint32_t* heldCount, uint32_t* boxCount) {
+    if (!p || !drawCount || !heldCount || !p->setupDone) return BRMI_ERR_INVALID;
+    BRMI_HIP(p, hipDeviceSynchronize());
+    uint32_t nd = 0, nh = 0;      // (as the kernel left them: a count beyond the list's capacity is the caller's to see)
+    BRMI_HIP(p, hipMemcpy(&nd, p->counters() + CNT_DRAW1, 4, hipMemcpyDeviceToHost));
+    BRMI_HIP(p, hipMemcpy(&nh, p->counters() + CNT_HELD1, 4, hipMemcpyDeviceToHost));
+    if (!p->holdEnabled) nd = nh = 0;
+    *drawCount = nd; *heldCount = nh;
+    if (boxCount) *boxCount = p->tables.totalBoxes;
+    const uint32_t rd = std::min(std::min(nd, drawCapacity), p->cfg.maxVisibleClusters), rh = std::min(std::min(nh, heldCapacity), p->cfg.maxVisibleClusters);
+    if (draw && rd) BRMI_HIP(p, hipMemcpy(draw, p->wsPtr<uint32_t>(p->ws.drawList), (size_t)rd * 4, hipMemcpyDeviceToHost));
+    if (heldBoxes && rh) {
+        std::vector<HeldRecord> rec(rh);
+        BRMI_HIP(p, hipMemcpy(rec.data(), p->wsPtr<HeldRecord>(p->ws.heldRecords), rec.size() * sizeof(HeldRecord), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < rec.size(); i++) heldBoxes[i] = rec[i].boxIndex;
+    }
+    return BRMI_OK;
+}
+
 int brmi_debug_wide_triangles(brmi_pass* p, uint32_t out[3]) {
     if (!p || !out || !p->setupDone) return BRMI_ERR_INVALID;
     BRMI_HIP(p, hipDeviceSynchronize());

@@ -1207,9 +1207,20 @@ __global__ void __launch_bounds__(256) k_cull_flat_level(CullArgs a, uint32_t le
 // (3 x 136 of a SIMD's 512 registers taken) each of them waited for a shading wave to retire -- k_cull_hierarchy 38 us alone, 97 us in flight
 // (kernel trace), on the chain the next frame waits for.  This kernel's waves fit the gap (<= 104 registers), and the light clustering of a split
 // frame runs on the shading stream (brmi_execute_split).
-template <int SIDE, typename Residency>
-__global__ void __launch_bounds__(256) k_cull_clusters(CullArgs a, const BucketRecord* buckets, TempVisible* temp, uint32_t* bitmask, uint8_t* blockDirty,
-                                                       typename std::conditional<SIDE == 1, LcRide, typename std::conditional<SIDE == 2, ClearRide, NoSide>::type>::type ride, Residency res) {
+// HOLD (phase 1 of a frame that holds clusters back): a surviving lane also predicts the draw list -- is the meshlet's BOX behind the chain its sphere was just
+// tested against (box_behind_chain, brmi_internal.h)? -- and appends the verdict with its record: held / boxIndex / perObject of TempVisible.  The question does not
+// depend on the cluster's rank, and here its inputs (the instance record, the object's index, the chain) are at hand and the survivors are spread over every wave of
+// the launch; in k_scatter_visible, where it used to be asked, all 64 lanes of a wave queued on the same chain of dependent loads between the scan and the rasteriser.
+// The other instantiations keep their code and registers.
+// (box_behind_chain asks the question the re-test asks -- of the PREVIOUS frame's chain with the previous frame's matrices.  The reference's own test asks it of the
+// meshlet's SPHERE with four texels of a coarser mip, and lets through twice the clusters that own a pixel: profiles/r06_experiments.md -- a box's near corner is
+// the surface's, a sphere's near point half a cluster in front of it.)  The prediction's inputs beside the chain: the per-meshlet boxes, the per-object constants.
+struct HoldPredict { const MeshletBox* boxes; const uint32_t* pageBoxBase; const float* objConst; uint32_t maxTexels; BoxViewport vp; };
+template <int SIDE> using ClusterCullRide = typename std::conditional<SIDE == 1, LcRide, typename std::conditional<SIDE == 2, ClearRide, NoSide>::type>::type;
+// (the body of both entry points below: k_cull_clusters, HOLD = false, keeps its name and arguments -- tests and profiles know it by them -- and k_cull_clusters_hold)
+template <int SIDE, bool HOLD, typename Residency>
+__device__ __forceinline__ void cull_clusters(const CullArgs& a, const BucketRecord* buckets, TempVisible* temp, uint32_t* bitmask, uint8_t* blockDirty, const ClusterCullRide<SIDE>& ride,
+                                              const typename std::conditional<HOLD, HoldPredict, NoSide>::type& hold, const Residency& res) {
     uint32_t mainBlocks = gridDim.x;
     if constexpr (SIDE == 1) {
         mainBlocks = ride.mainBlocks;
@@ -1230,9 +1241,13 @@ __global__ void __launch_bounds__(256) k_cull_clusters(CullArgs a, const BucketR
     const brmi_camera* cam = sc.cameras + viewId;
     const brmi_culling_camera* lodCam = sc.cullingCameras + viewId;
     const bool ortho = cam->isOrtho != 0;
-    const f3 camPos{lodCam->positionWorldSpace[0], lodCam->positionWorldSpace[1], lodCam->positionWorldSpace[2]};
-    const float zNear = lodCam->zNear, threshold = lodCam->errorOverDistanceThreshold;
-    const m4 view = load_m4(&cam->view[0][0]);
+    // (HOLD: the loop's invariants as scalars -- the same values in every lane: `cam` and `lodCam` are the launch's ONE camera, perFrame->mainCameraIndex, read here before any
+    // lane diverges; a camera chosen per lane would have to drop this -- as some twenty vector registers beside the box test's 24 corner terms, its matrices and its box they cost the kernel an occupancy step)
+    const auto uni = [](float v) { if constexpr (HOLD) return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); else return v; };
+    const f3 camPos{uni(lodCam->positionWorldSpace[0]), uni(lodCam->positionWorldSpace[1]), uni(lodCam->positionWorldSpace[2])};
+    const float zNear = uni(lodCam->zNear), threshold = uni(lodCam->errorOverDistanceThreshold);
+    m4 view = load_m4(&cam->view[0][0]);
+    if constexpr (HOLD) for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) view.m[r][c] = uni(view.m[r][c]);
     uint32_t* tempCount = &a.counters[a.phase == 2 ? CNT_TEMP_VISIBLE2 : CNT_TEMP_VISIBLE];
     // one lane per (bucket, meshlet-in-bucket): `factor` lanes cooperate on a record
     const uint64_t totalLanes = (uint64_t)bucketCount * a.factor;
@@ -1244,6 +1259,7 @@ __global__ void __launch_bounds__(256) k_cull_clusters(CullArgs a, const BucketR
         bool survives = false, occluded = false, tested = false;
         uint4 packed = make_uint4(0, 0, 0, 0);
         uint32_t bit = 0;
+        uint32_t perObject = 0u; bool boxed = false;      // (HOLD: what the draw list's prediction needs of a survivor; boxed: its mesh is not skinned)
         uint4 againLo = make_uint4(0u, 0u, 0u, 0u); uint2 againHi = make_uint2(0u, 0u);      // the replay record of an occluded meshlet (as plain words: a BucketRecord object here left an unused 36 B stack slot in the kernel's descriptor)
         if (idx < totalLanes) {
             const uint32_t bi = (uint32_t)(idx / a.factor), m = (uint32_t)(idx % a.factor);
@@ -1260,8 +1276,8 @@ __global__ void __launch_bounds__(256) k_cull_clusters(CullArgs a, const BucketR
                     float4 bounds = *reinterpret_cast<const float4*>(desc->bounds);
                     const uint32_t triAndRefined = desc->triangleCountAndRefinedGroup;
                     const brmi_per_mesh_instance inst = sc.perMeshInstance[b.instanceIndex];
-                    if ((sc.perMesh[inst.perMeshBufferIndex].vertexFlags & BRMI_VERTEX_SKINNED) != 0u)
-                        bounds = skinned_meshlet_bounds(sc, desc, hdr, slab + b.pageSlabByteOffset, inst.skinningInstanceSlot, bounds);
+                    const bool skinned = (sc.perMesh[inst.perMeshBufferIndex].vertexFlags & BRMI_VERTEX_SKINNED) != 0u;
+                    if (skinned) bounds = skinned_meshlet_bounds(sc, desc, hdr, slab + b.pageSlabByteOffset, inst.skinningInstanceSlot, bounds);
                     const brmi_clod_mesh_metadata* md = sc.meshMetadata + sc.clodOffsets[b.instanceIndex].clodMeshMetadataIndex;
                     const m4 model = load_m4(&sc.perObject[inst.perObjectBufferIndex].model[0][0]);
                     const float scale = max_axis_scale(model);
@@ -1286,6 +1302,7 @@ __global__ void __launch_bounds__(256) k_cull_clusters(CullArgs a, const BucketR
                     if (survives) {
                         packed = pack_visible_cluster(viewId, b.instanceIndex, lm, b.groupIdPacked & 0x7FFFFFFFu, b.pageSlabDescriptorIndex, b.pageSlabByteOffset);
                         bit = b.firstBit + m;
+                        if constexpr (HOLD) { perObject = inst.perObjectBufferIndex; boxed = !skinned; }
                     }
                 }
             }
@@ -1314,13 +1331,35 @@ __global__ void __launch_bounds__(256) k_cull_clusters(CullArgs a, const BucketR
         }
         if (survives) {
             if (slot < a.visibleCapacity) {
-                TempVisible t; t.packed = packed; t.bit = bit; t.pad0 = t.pad1 = t.pad2 = 0;
-                temp[slot] = t;
                 atomicOr(&bitmask[bit >> 5], 1u << (bit & 31u));
                 blockDirty[bit >> 16] = 1;        // (the bit's 2048-word block of the ranking; every writer stores 1)
+                uint32_t held = 0u, boxIndex = HOLD ? 0xFFFFFFFFu : 0u;      // (the plain forms store three zeros, as they did)
+                if constexpr (HOLD) {
+                    // (round 6: the cluster is visible as far as the reference's tests go; is it worth drawing FIRST?  Previous frame's chain, previous frame's matrices.  At the
+                    // iteration's end, not among the reference's tests: their matrices, bounds and replay record are dead here, and the box's corners take the registers they held.)
+                    const uint32_t boxBase = boxed ? hold.pageBoxBase[(size_t)vc_slab(packed) * 1024u + (vc_page_offset(packed) >> 18)] : 0xFFFFFFFFu;
+                    if (boxBase != 0xFFFFFFFFu) {
+                        boxIndex = boxBase + vc_meshlet(packed);
+                        const MeshletBox bx = hold.boxes[boxIndex];
+                        const float* oc = hold.objConst + (size_t)perObject * OBJ_CONST_FLOATS;
+                        if (bx.valid && box_behind_chain(a.hzb, bx, oc + 36, oc + 52, hold.vp, hold.maxTexels)) held = 1u;
+                    }
+                }
+                TempVisible t; t.packed = packed; t.bit = bit; t.held = held; t.boxIndex = boxIndex; t.perObject = perObject;
+                temp[slot] = t;
             } else atomicAdd(&a.counters[CNT_DROPPED_CLUSTERS], 1u);
         }
     }
+}
+
+template <int SIDE, typename Residency>
+__global__ void __launch_bounds__(256) k_cull_clusters(CullArgs a, const BucketRecord* buckets, TempVisible* temp, uint32_t* bitmask, uint8_t* blockDirty,
+                                                       typename std::conditional<SIDE == 1, LcRide, typename std::conditional<SIDE == 2, ClearRide, NoSide>::type>::type ride, Residency res) {
+    cull_clusters<SIDE, false>(a, buckets, temp, bitmask, blockDirty, ride, NoSide{}, res);
+}
+template <int SIDE, typename Residency>
+__global__ void __launch_bounds__(256) k_cull_clusters_hold(CullArgs a, const BucketRecord* buckets, TempVisible* temp, uint32_t* bitmask, uint8_t* blockDirty, ClusterCullRide<SIDE> ride, HoldPredict hold, Residency res) {
+    cull_clusters<SIDE, true>(a, buckets, temp, bitmask, blockDirty, ride, hold, res);
 }
 
 // rank = exclusive popcount scan over the bitmask ----------------------------------------------
@@ -1459,13 +1498,8 @@ struct LocalRank { uint32_t totalWords, outIndex, usedIndex; uint32_t* hostFeedb
 // Round 6: the lists of a frame that holds clusters back (brmi_raster.hip).  drawList == nullptr: every cluster of the visible list is rasterised in list order, as before.
 struct DrawLists {
     uint32_t* drawList; HeldRecord* held; uint32_t countAll;      // countAll: phase 2 of such a frame -- every placed cluster is drawn and counts
-    // the prediction's inputs (phase 1): the chain the reference's test just read, the per-meshlet boxes, the per-object constants, the chain's size
-    // (box_behind_chain, brmi_internal.h: the same question the re-test asks -- of the PREVIOUS frame's chain with the previous frame's matrices.  The reference's own
-    // test asks it of the meshlet's SPHERE with four texels of a coarser mip, and lets through twice the clusters that own a pixel: profiles/r06_experiments.md --
-    // a box's near corner is the surface's, a sphere's near point half a cluster in front of it.)
-    const MeshletBox* boxes; const uint32_t* pageBoxBase; const float* objConst; uint32_t maxTexels; BoxViewport vp; HzbDesc hzb;
 };
-template <bool LOCAL_RANK, bool HOLD>      // HOLD: phase 1 of a frame that holds clusters back (the prediction and the two lists; the plain instantiations keep their registers)
+template <bool LOCAL_RANK, bool HOLD>      // HOLD: phase 1 of a frame that holds clusters back (the two lists, by the prediction k_cull_clusters_hold left in the records; the plain instantiations keep their registers)
 __global__ void __launch_bounds__(256) k_scatter_visible(const TempVisible* temp, uint32_t* counters, uint32_t tempCountIndex, const uint32_t* bitmask,
                                                         const uint32_t* wordPrefix, uint4* visible, uint32_t baseIndexCounter, uint32_t capacity, uint32_t visibleCapacity,
                                                         brmi_scene_buffers sc, ClusterSetup* setup, uint32_t resolveCapacity, ClusterUv* clusterUv, LocalRank lr, DrawLists dl) {
@@ -1525,18 +1559,7 @@ __global__ void __launch_bounds__(256) k_scatter_visible(const TempVisible* temp
                 verts = min((desc->bitsAndVertexCount >> 24) & 0xFFu, BRMI_MESHLET_MAX_VERTS);
                 tris = min(desc->triangleCountAndRefinedGroup & 0xFFFFu, BRMI_MESHLET_MAX_TRIS);
                 placed = 1;
-                if (HOLD) {
-                    // (round 6: the cluster is visible as far as the reference's tests go and has its place in the list; is it worth drawing FIRST?)
-                    const brmi_per_mesh_instance inst = sc.perMeshInstance[vc_instance(t.packed)];
-                    perObject = inst.perObjectBufferIndex;
-                    const uint32_t boxBase = dl.pageBoxBase[(size_t)vc_slab(t.packed) * 1024u + (pageOff >> 18)];
-                    if (boxBase != 0xFFFFFFFFu && (sc.perMesh[inst.perMeshBufferIndex].vertexFlags & BRMI_VERTEX_SKINNED) == 0u) {
-                        boxIndex = boxBase + vc_meshlet(t.packed);
-                        const MeshletBox bx = dl.boxes[boxIndex];
-                        const float* oc = dl.objConst + (size_t)perObject * OBJ_CONST_FLOATS;
-                        if (bx.valid && box_behind_chain(dl.hzb, bx, oc + 36, oc + 52, dl.vp, dl.maxTexels)) held = 1u;
-                    }
-                }
+                if (HOLD) { held = t.held; boxIndex = t.boxIndex; perObject = t.perObject; }      // (is it worth drawing FIRST?  k_cull_clusters_hold has asked)
             }
         }
         uint32_t inclV = verts, inclT = tris;
@@ -1759,15 +1782,26 @@ int launch_cull(brmi_pass* p, FrameCtx& ctx, uint32_t phase, hipStream_t s) {
         smallGrid = std::max(smallGrid, grid_for((uint64_t)std::min<uint32_t>(lastBuckets, p->cfg.maxTraversalRecords) * f, 256, 8192));
         scatterGrid = std::max(scatterGrid, grid_for(std::min<uint32_t>(lastVisible, p->cfg.maxVisibleClusters), 256, 8192));
     }
+    // (phase 1 of a frame that holds clusters back: the instantiation that also predicts the draw list)
+    const bool holdLists = phase == 1 && p->holdThisFrame;
+    const HoldPredict predict{p->wsPtr<MeshletBox>(p->ws.meshletBoxes), p->wsPtr<uint32_t>(p->ws.pageBoxBase), p->wsPtr<float>(p->ws.objConst), p->holdMaxTexels,
+                              BoxViewport{(float)p->cfg.width, (float)p->cfg.height, 0.0f, 0.0f, 0, (int)p->bandY0, (int)p->cfg.width - 1, (int)p->bandY1 - 1}};
+    auto launch_cluster_cull = [&](auto side, uint32_t riderBlocks, auto ride) {
+        constexpr int SIDE = decltype(side)::value;
+        with_residency([&](auto res) {
+            if (holdLists) hipLaunchKernelGGL((k_cull_clusters_hold<SIDE, decltype(res)>), dim3(smallGrid + riderBlocks), dim3(256), 0, s, a, (const BucketRecord*)buckets, temp, bitmask, blockDirty, ride, predict, res);
+            else hipLaunchKernelGGL((k_cull_clusters<SIDE, decltype(res)>), dim3(smallGrid + riderBlocks), dim3(256), 0, s, a, (const BucketRecord*)buckets, temp, bitmask, blockDirty, ride, res);
+        });
+    };
     if (lightGridRides) {
-        with_residency([&](auto res) { hipLaunchKernelGGL((k_cull_clusters<1, decltype(res)>), dim3(smallGrid + (p->numLightClusters + 3u) / 4u), dim3(256), 0, s, a, (const BucketRecord*)buckets, temp, bitmask, blockDirty, LcRide{smallGrid, cluster_args_of(p)}, res); });
+        launch_cluster_cull(std::integral_constant<int, 1>{}, (p->numLightClusters + 3u) / 4u, LcRide{smallGrid, cluster_args_of(p)});
         ctx.lightGridBuilt = true;
     } else if (carrier == VisibilityClear::OnClusterCull) {
         const uint32_t clearBlocks = 2048;
-        with_residency([&](auto res) { hipLaunchKernelGGL((k_cull_clusters<2, decltype(res)>), dim3(smallGrid + clearBlocks), dim3(256), 0, s, a, (const BucketRecord*)buckets, temp, bitmask, blockDirty, ClearRide{smallGrid, reinterpret_cast<ulonglong2*>(static_cast<unsigned long long*>(p->res[BRMI_RES_VISIBILITY]) + p->bandFirstPixel), p->bandPixelCount >> 1, clearBlocks}, res); });
+        launch_cluster_cull(std::integral_constant<int, 2>{}, clearBlocks, ClearRide{smallGrid, reinterpret_cast<ulonglong2*>(static_cast<unsigned long long*>(p->res[BRMI_RES_VISIBILITY]) + p->bandFirstPixel), p->bandPixelCount >> 1, clearBlocks});
         ctx.visibilityCleared = true;
-    } else with_residency([&](auto res) { hipLaunchKernelGGL((k_cull_clusters<0, decltype(res)>), dim3(smallGrid), dim3(256), 0, s, a, (const BucketRecord*)buckets, temp, bitmask, blockDirty, NoSide{}, res); });
-    BRMI_LAUNCH_CHECK(p, "k_cull_clusters");
+    } else launch_cluster_cull(std::integral_constant<int, 0>{}, 0u, NoSide{});
+    BRMI_LAUNCH_CHECK(p, holdLists ? "k_cull_clusters_hold" : "k_cull_clusters");
     // phase 2 appends behind the phase-1 clusters: its capacity is what phase 1 left
     const uint32_t outIndex = phase == 1 ? CNT_VISIBLE : CNT_VISIBLE2, usedIndex = phase == 1 ? 0xFFFFFFFFu : (uint32_t)CNT_VISIBLE;
     // every workgroup of the scatter scanning the bitmask itself pays off while the bitmask is small (BASELINE-class scenes: ~1-4 k words);
@@ -1796,11 +1830,9 @@ int launch_cull(brmi_pass* p, FrameCtx& ctx, uint32_t phase, hipStream_t s) {
         hipLaunchKernelGGL(kernel, dim3(scatterGrid), dim3(256), 0, s, temp, p->counters(), (uint32_t)(phase == 1 ? CNT_TEMP_VISIBLE : CNT_TEMP_VISIBLE2), bitmask, wordPrefix,
                            static_cast<uint4*>(p->res[BRMI_RES_VISIBLE_CLUSTERS]), phase == 1 ? 0xFFFFFFFFu : (uint32_t)CNT_VISIBLE, p->cfg.maxVisibleClusters, p->cfg.maxVisibleClusters, p->scene, p->wsPtr<ClusterSetup>(p->ws.clusterSetup), arenaCapacity,
                            (p->tables.hasTextures || p->tables.hasAlphaTest || p->tables.hasVertexColors) ? p->wsPtr<ClusterUv>(p->ws.clusterUv) : nullptr, LocalRank{p->totalWords, outIndex, usedIndex, feedback},
-                           (phase == 1 && p->holdThisFrame) ? DrawLists{p->wsPtr<uint32_t>(p->ws.drawList), p->wsPtr<HeldRecord>(p->ws.heldRecords), 0u, p->wsPtr<MeshletBox>(p->ws.meshletBoxes), p->wsPtr<uint32_t>(p->ws.pageBoxBase),
-                                                                      p->wsPtr<float>(p->ws.objConst), p->holdMaxTexels, BoxViewport{(float)p->cfg.width, (float)p->cfg.height, 0.0f, 0.0f, 0, (int)p->bandY0, (int)p->cfg.width - 1, (int)p->bandY1 - 1}, a.hzb}
-                                                          : DrawLists{nullptr, nullptr, p->holdThisFrame ? 1u : 0u, nullptr, nullptr, nullptr, 0u, BoxViewport{}, HzbDesc{}});
+                           (phase == 1 && p->holdThisFrame) ? DrawLists{p->wsPtr<uint32_t>(p->ws.drawList), p->wsPtr<HeldRecord>(p->ws.heldRecords), 0u}
+                                                          : DrawLists{nullptr, nullptr, p->holdThisFrame ? 1u : 0u});
     };
-    const bool holdLists = phase == 1 && p->holdThisFrame;
     if (localRank) { if (holdLists) scatter(k_scatter_visible<true, true>); else scatter(k_scatter_visible<true, false>); }
     else { if (holdLists) scatter(k_scatter_visible<false, true>); else scatter(k_scatter_visible<false, false>); }
     BRMI_LAUNCH_CHECK(p, "compaction");

@@ -81,7 +81,7 @@ struct BucketRecord {                                                           
     uint32_t instanceIndex, groupIdPacked, meshletIndexAndCount, pageSlabDescriptorIndex;
     uint32_t pageSlabByteOffset, firstBit, pad0, pad1;
 };
-struct TempVisible { uint4 packed; uint32_t bit, pad0, pad1, pad2; };                // 32 B
+struct TempVisible { uint4 packed; uint32_t bit, held, boxIndex, perObject; };       // 32 B; the last three: the draw list's prediction (k_cull_clusters_hold), zero / none / zero elsewhere
 // Round 6: what the library keeps per meshlet BESIDE the reference's descriptor (whose only bound is a sphere): the object-space box of its vertices, made once per
 // brmi_setup from the page contents (k_meshlet_boxes).  Not part of the data contract; indexed by pageBoxBase[slab * 1024 + page] + meshlet.
 struct MeshletBox { float lo[3]; uint32_t valid; float hi[3]; uint32_t pad; };       // 32 B

@@ -240,6 +240,17 @@ class VisibilityRenderer:
         self._check(self.lib.brmi_debug_read_held(self._h, held.ctypes.data_as(C.POINTER(capi.u32)), len(held), C.byref(nh), late.ctypes.data_as(C.POINTER(capi.u32)), len(late), C.byref(nl)), "brmi_debug_read_held")
         return held[: nh.value], late[: nl.value]
 
+    def draw_list(self):
+        """(draw, held_boxes, box_count): the last frame's draw list (indices into visible_clusters(); the list's counter is checked against its capacity), the box-table
+        index of every held record in held_clusters()'s order, and the size of that table (brmi_debug_read_draw_list)."""
+        nd, nh, nb = capi.u32(), capi.u32(), capi.u32()
+        self._check(self.lib.brmi_debug_read_draw_list(self._h, None, 0, C.byref(nd), None, 0, C.byref(nh), C.byref(nb)), "brmi_debug_read_draw_list")
+        if nd.value > self.cfg.maxVisibleClusters or nh.value > self.cfg.maxVisibleClusters:
+            raise BrmiError(f"draw list of {nd.value} / held list of {nh.value} entries in buffers of {self.cfg.maxVisibleClusters}")
+        draw, boxes = np.zeros(max(1, nd.value), dtype=np.uint32), np.zeros(max(1, nh.value), dtype=np.uint32)
+        self._check(self.lib.brmi_debug_read_draw_list(self._h, draw.ctypes.data_as(C.POINTER(capi.u32)), len(draw), C.byref(nd), boxes.ctypes.data_as(C.POINTER(capi.u32)), len(boxes), C.byref(nh), C.byref(nb)), "brmi_debug_read_draw_list")
+        return draw[: nd.value], boxes[: nh.value], int(nb.value)
+
     def lean_clusters(self):
         """(1 if the last frame's phase-1 main launch was the lean rasteriser, clusters it left to the general launch, triangles queued for k_raster_emit, runs of
         them) -- brmi_debug_lean_clusters."""

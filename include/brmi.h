@@ -574,6 +574,10 @@ int brmi_debug_read_lean_queue(brmi_pass* pass, uint32_t stripe, uint32_t* runs,
 /* The last frame's draw-list decisions, for tests (waits for the device): indices into the visible-cluster buffer of the phase-1 clusters the culling held back
  * (`held`, up to heldCapacity entries; *heldCount = how many there were) and of those the late pass drew (`late`).  held minus late was never rasterised. */
 int brmi_debug_read_held(brmi_pass* pass, uint32_t* held, uint32_t heldCapacity, uint32_t* heldCount, uint32_t* late, uint32_t lateCapacity, uint32_t* lateCount);
+/* The other side of those decisions (waits for the device): the draw list -- indices of the phase-1 clusters the rasteriser took first (`draw`; *drawCount = the
+ * list's counter as the frame left it, unclamped) -- and, in the order of brmi_debug_read_held's `held`, the index of each held record's box in the library's
+ * per-meshlet box table (`heldBoxes`; *boxCount = the table's size when asked for).  draw and held partition the placed phase-1 clusters.  Buffers may be null. */
+int brmi_debug_read_draw_list(brmi_pass* pass, uint32_t* draw, uint32_t drawCapacity, uint32_t* drawCount, uint32_t* heldBoxes, uint32_t heldCapacity, uint32_t* heldCount, uint32_t* boxCount);
 
 /* Diagnostics: the first `bytes` of the raster bin-record region of the workspace; with bit 62 of `bytes` set, those bytes are zeroed instead (a following
  * frame's records can then be told from older ones).  Waits for the device. */
