@@ -302,7 +302,7 @@ void brmi_destroy(brmi_pass* p) {
     if (p->geometryDone) (void)hipEventDestroy(p->geometryDone);
     if (p->cullDone) (void)hipEventDestroy(p->cullDone);
     if (p->frameDone) (void)hipEventDestroy(p->frameDone);
-    if (p->phase2FeedbackHost) (void)hipHostFree(p->phase2FeedbackHost);
+    p->feedback.release();
     delete p;
 }
 

@@ -44,7 +44,7 @@ struct CullArgs {
     // the few wider ones by the level-per-launch kernels (all lanes of the chip on one level); the latter skip instances narrower than this
     const uint32_t* meshLevelWidth; uint32_t levelKernelsWidthLo;
     const FlatNode* flatNodes; const FlatLeaf* flatLeaves; const InstanceWalk* instanceWalk;     // flat traversal of small hierarchies (brmi_internal.h)
-    uint32_t* feedback;                  // host-mapped words (brmi_pass::ensureFeedback) or null: word 2 = phase 1's bucket records (the host sizes the next frames' launches by it)
+    uint32_t* feedback;                  // the host-mapped block (HostFeedback::devBlock) or null: FB_BUCKETS1 / FB_BUCKETS2 are stored here
     uint32_t wideFlat;                   // phase 1: hierarchies of 257 .. 8192 nodes are k_cull_flat_wide's (the walk skips them)
     uint32_t packedFlat;                 // phase 1: the launch's first ceil(draws / 8) waves take eight draws each (hierarchies of <= 8 nodes)
 };
@@ -1236,7 +1236,7 @@ __device__ __forceinline__ void cull_clusters(const CullArgs& a, const BucketRec
     }
     const brmi_scene_buffers& sc = a.sc;
     const uint32_t bucketCount = min(a.counters[a.bucketCounter], a.recordCapacity);
-    if (a.feedback && blockIdx.x == 0u && threadIdx.x == 0u) __hip_atomic_store(a.feedback + (a.phase == 1u ? 2 : 4), bucketCount, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (a.feedback && blockIdx.x == 0u && threadIdx.x == 0u) __hip_atomic_store(a.feedback + (a.phase == 1u ? FB_BUCKETS1 : FB_BUCKETS2), bucketCount, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     const uint32_t viewId = sc.perFrame->mainCameraIndex;
     const brmi_camera* cam = sc.cameras + viewId;
     const brmi_culling_camera* lodCam = sc.cullingCameras + viewId;
@@ -1659,7 +1659,7 @@ int launch_cull(brmi_pass* p, FrameCtx& ctx, uint32_t phase, hipStream_t s) {
     uint32_t f = p->cfg.phase2ExpansionFactor; f = f < 1 ? 1 : (f > 64 ? 64 : f);
     { uint32_t n = 1; for (uint32_t c = 2; c <= 64; c <<= 1) if (c <= f) n = c; f = n; }
     a.factor = f; a.phase = phase; a.packedFlat = 0u; a.wideFlat = 0u;
-    a.feedback = p->ensureFeedback() ? p->phase2FeedbackDev : nullptr;
+    a.feedback = p->feedback.ensure() ? p->feedback.devBlock() : nullptr;
 
     // the band test's two planes through the eye only bound a row band under a symmetric perspective projection: an orthographic or
     // off-centre camera keeps the frustum test alone (the rasteriser's row filter still confines the band; nothing is lost but the early cull)
@@ -1676,8 +1676,7 @@ int launch_cull(brmi_pass* p, FrameCtx& ctx, uint32_t phase, hipStream_t s) {
     if (phase == 1) {
         // Round 6: this frame holds clusters back when the pass can (brmi_set_scene), the previous frame's chain is there to predict from, and the frames before had
         // enough clusters for the two extra launches to pay (the count is a host-mapped word a frame or two old; either way the same image)
-        const uint32_t lastVisible = p->phase2FeedbackHost ? reinterpret_cast<volatile uint32_t*>(p->phase2FeedbackHost)[3] : 0u;
-        const uint32_t lastPhase2 = p->phase2FeedbackHost ? reinterpret_cast<volatile uint32_t*>(p->phase2FeedbackHost)[0] : 0xFFFFFFFFu;
+        const uint32_t lastVisible = p->feedback.last(FB_PLACED1, 0u), lastPhase2 = p->feedback.last(FB_PLACED2, 0xFFFFFFFFu);
         // (a still camera's small frame too -- but not a frame of a few hundred clusters: a rank's sky band of 195 clusters pays the three extra launches for nothing; holdFloor)
         p->holdThisFrame = p->holdEnabled && a.occlusion != 0u && (p->holdMinClusters == 0u || (lastVisible != 0xFFFFFFFFu && lastVisible >= p->holdMinClusters) ||
                                                                   (p->holdStillMax != 0u && lastPhase2 < p->holdStillMax && lastVisible != 0xFFFFFFFFu && lastVisible >= p->holdFloor));
@@ -1775,13 +1774,11 @@ int launch_cull(brmi_pass* p, FrameCtx& ctx, uint32_t phase, hipStream_t s) {
     // Frames of hundreds of thousands of records (Zorah-class: 180 k bucket records, 490 k survivors) need more than that: a lane's chain of dependent loads
     // (record -> page header -> descriptor -> instance -> object -> depth chain) three or four times over was most of both kernels.  The counts of the frames
     // before (host-mapped words the kernels write; read without waiting, any value is safe: the kernels stride their grids) size the launches.
+    // (without a block both counts read 0, which leaves the sizes below as they start; 0xFFFFFFFF = unknown is clamped)
     uint32_t smallGrid = phase == 1 ? 512u : 128u, scatterGrid = smallGrid;
-    if (p->phase2FeedbackHost) {
-        const uint32_t lastBuckets = reinterpret_cast<volatile uint32_t*>(p->phase2FeedbackHost)[phase == 1 ? 2 : 4];
-        const uint32_t lastVisible = reinterpret_cast<volatile uint32_t*>(p->phase2FeedbackHost)[phase == 1 ? 3 : 0];      // (0xFFFFFFFF = unknown is clamped below)
-        smallGrid = std::max(smallGrid, grid_for((uint64_t)std::min<uint32_t>(lastBuckets, p->cfg.maxTraversalRecords) * f, 256, 8192));
-        scatterGrid = std::max(scatterGrid, grid_for(std::min<uint32_t>(lastVisible, p->cfg.maxVisibleClusters), 256, 8192));
-    }
+    const uint32_t lastBuckets = p->feedback.last(phase == 1 ? FB_BUCKETS1 : FB_BUCKETS2, 0u), lastPlaced = p->feedback.last(phase == 1 ? FB_PLACED1 : FB_PLACED2, 0u);
+    smallGrid = std::max(smallGrid, grid_for((uint64_t)std::min<uint32_t>(lastBuckets, p->cfg.maxTraversalRecords) * f, 256, 8192));
+    scatterGrid = std::max(scatterGrid, grid_for(std::min<uint32_t>(lastPlaced, p->cfg.maxVisibleClusters), 256, 8192));
     // (phase 1 of a frame that holds clusters back: the instantiation that also predicts the draw list)
     const bool holdLists = phase == 1 && p->holdThisFrame;
     const HoldPredict predict{p->wsPtr<MeshletBox>(p->ws.meshletBoxes), p->wsPtr<uint32_t>(p->ws.pageBoxBase), p->wsPtr<float>(p->ws.objConst), p->holdMaxTexels,
@@ -1807,8 +1804,7 @@ int launch_cull(brmi_pass* p, FrameCtx& ctx, uint32_t phase, hipStream_t s) {
     // every workgroup of the scatter scanning the bitmask itself pays off while the bitmask is small (BASELINE-class scenes: ~1-4 k words);
     // from 8 k words on the three scan launches are faster (dense frame, 25 k words: 27 us against 55 us per phase)
     // phase 2: the ranking kernel also tells the host how many clusters it placed (launch_raster's hint for the frames that follow)
-    if (phase == 2 && p->phase2DirectMax != 0u) (void)p->ensureFeedback();
-    uint32_t* feedback = phase == 2 ? p->phase2FeedbackDev : (p->phase2FeedbackDev ? p->phase2FeedbackDev + 3 : nullptr);      // (phase 1: word 3, the sizes of the next frames' launches)
+    uint32_t* feedback = p->feedback.dev(phase == 2 ? FB_PLACED2 : FB_PLACED1);      // (phase 1: the sizes of the next frames' launches)
     const bool localRank = p->totalWords <= LOCAL_RANK_WORDS && !p->forceLevelKernels;
     if (localRank) {
         // ranked inside the scatter kernel

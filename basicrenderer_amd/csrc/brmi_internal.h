@@ -293,6 +293,45 @@ struct FrameCtx {
     bool chainDirtyBlocksKnown = false;       // the last rasteriser pass recorded the 32 x 32 px blocks it may have touched (the chain build behind it skips the others)
 };
 
+// What the device tells the host about the frames before: one 64 B host-mapped block per pass.  Kernels store a word with a relaxed system-scope atomic; the host reads
+// it without waiting, a frame or two late, and only ever chooses between launches that give the same image (a grid size, one of two equally exact paths), so any
+// value is safe.  Writers and readers of every word: DESIGN.md 6b.
+enum FeedbackWord : uint32_t {
+    FB_PLACED2 = 0,          // clusters phase 2 placed (0xFFFFFFFF: not known yet)
+    FB_RESOLVE_INLINE = 1,   // frames like the last should resolve in place, without the per-cluster tables
+    FB_BUCKETS1 = 2,         // bucket records of phase 1
+    FB_PLACED1 = 3,          // clusters phase 1 placed
+    FB_BUCKETS2 = 4,         // bucket records of phase 2
+    FB_LATE = 5,             // clusters of the late list
+    FB_HELD = 6,             // clusters held back
+    FB_WIDE1 = 7,            // phase 1's wide triangles
+    FB_LEAN_COUNT = 8,       // clusters of the lean main launch
+    FB_GENERAL_COUNT = 9,    // ... and of the general launch behind it
+    FB_WORD_COUNT
+};
+class HostFeedback {
+public:
+    static constexpr uint32_t kWords = 16;
+    // makes the block at first use; false: there is none (every reader below then answers with its caller's always-safe value)
+    bool ensure() {
+        if (host) return true;
+        uint32_t* h = nullptr; uint32_t* d = nullptr;
+        if (hipHostMalloc(reinterpret_cast<void**>(&h), kWords * sizeof(uint32_t), hipHostMallocMapped) != hipSuccess) return false;
+        for (uint32_t k = 0; k < kWords; k++) h[k] = k == FB_PLACED2 ? 0xFFFFFFFFu : 0u;
+        if (hipHostGetDevicePointer(reinterpret_cast<void**>(&d), h, 0) != hipSuccess) { (void)hipHostFree(h); return false; }
+        host = h; device = d;
+        return true;
+    }
+    void release() { if (host) (void)hipHostFree(const_cast<uint32_t*>(host)); host = nullptr; device = nullptr; }
+    uint32_t last(FeedbackWord w, uint32_t ifNone) const { return host ? host[w] : ifNone; }
+    void store(FeedbackWord w, uint32_t v) { if (host) host[w] = v; }
+    uint32_t* dev(FeedbackWord w) const { return device ? device + w : nullptr; }
+    uint32_t* devBlock() const { return device; }      // for the kernels that pick their word themselves (CullArgs::feedback, GBufferArgs::hostFeedback)
+private:
+    volatile uint32_t* host = nullptr; uint32_t* device = nullptr;
+};
+static_assert(FB_WORD_COUNT <= HostFeedback::kWords, "the feedback words must fit the block");
+
 }  // namespace brmi
 
 struct brmi_pass {
@@ -343,16 +382,8 @@ struct brmi_pass {
     std::vector<float> sliceStartHost; float sliceKey[3] = {0, 0, 0}; uint32_t sliceKeyN[2] = {0, 0};   // slice starts of the light-cluster grid and the inputs they were made from
     // Phase 2 of a frame usually draws nothing or a few dozen clusters; then its triangles all take the row re-deal with global atomics (one
     // launch instead of k_raster + plan + bins).  Which it is, the host learns from the frames before: the ranking kernel of phase 2 also stores
-    // the survivor count in a host-mapped word that launch_raster reads without waiting (any value is safe: both paths draw the same keys).
-    uint32_t* phase2FeedbackHost = nullptr; uint32_t* phase2FeedbackDev = nullptr;      // word 0: phase-2 survivors; word 1: frames like the last ones should resolve without the per-cluster tables (resolve_inline_frame)
-    bool ensureFeedback() {          // the 64 B host-mapped block, made at first use; false: none (the callers then take their always-safe paths)
-        if (phase2FeedbackHost) return true;
-        if (hipHostMalloc(reinterpret_cast<void**>(&phase2FeedbackHost), 64, hipHostMallocMapped) != hipSuccess) { phase2FeedbackHost = nullptr; return false; }
-        phase2FeedbackHost[0] = 0xFFFFFFFFu; phase2FeedbackHost[1] = 0u;           // unknown: the general paths (word 1: the per-cluster resolve tables)
-        for (int k = 2; k < 16; k++) phase2FeedbackHost[k] = 0u;                  // word 2: phase 1's bucket records, word 3: phase 1's visible clusters (launch sizes of the frames that follow)
-        if (hipHostGetDevicePointer(reinterpret_cast<void**>(&phase2FeedbackDev), phase2FeedbackHost, 0) != hipSuccess) { (void)hipHostFree(phase2FeedbackHost); phase2FeedbackHost = nullptr; phase2FeedbackDev = nullptr; return false; }
-        return true;
-    }
+    // the survivor count in a host-mapped word (FB_PLACED2) that launch_raster reads without waiting (any value is safe: both paths draw the same keys).
+    brmi::HostFeedback feedback;      // released by brmi_destroy
     uint32_t phase2DirectMax = 128;   // BRMI_PHASE2_DIRECT_MAX: direct rasterisation while the last known phase-2 count is at most this (0: always bins).  Round 5: 256 -> 128 -- a camera that
                                       // moves fast leaves phase 2 two to four hundred clusters of large near triangles, which the row re-deal walks in few lanes: path_fast raster2 0.12 -> 0.065 ms
                                       // (0.648 -> 0.625 ms per frame); the slow path (30 - 80 clusters) and the still camera keep the one-launch form (sweep: profiles/r05_experiments.md)

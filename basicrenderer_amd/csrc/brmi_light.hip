@@ -272,47 +272,27 @@ static int launch_shade_range(brmi_pass* p, bool sharesChip, hipStream_t s, uint
     // 8192 workgroups of four waves, four tiles per wave at 4K: against 4096 (eight tiles per wave) the kernel's tail is shorter (233 -> 226 us)
     // and, with another frame's geometry half in flight beside it, slots come free twice as often for that half's high-priority launches
     // (Bistro 4K, two frames in flight: 0.436 -> 0.413 ms per frame; 16384: 0.425, 2048: 0.49)
-    // a bound environment (brmi_set_environment) selects the k_shade_ibl instantiations; without one the launches are the ones they always were
-    if (p->shadows.on) {      // brmi_set_shadows: the same choice among the three families, each with the shadow test in its light loop
-#define BRMI_LAUNCH_SHADOWED(K) do { \
-        if (sharesChip) hipLaunchKernelGGL((K<0, BRMI_SHADE_WAVES>), dim3(std::max(256u, p->shadeGridShared / share)), dim3(256), 0, s, a); \
-        else hipLaunchKernelGGL((K<0, BRMI_SHADE_WAVES_ALONE>), dim3(std::max(256u, 8192u / share)), dim3(256), 0, s, a); \
-        if (p->tables.hasCoat) hipLaunchKernelGGL(K<1>, dim3(512), dim3(256), 0, s, a); \
-        if (p->tables.hasFuzz) hipLaunchKernelGGL(K<2>, dim3(512), dim3(256), 0, s, a); \
-        if (p->tables.hasCoat && p->tables.hasFuzz) hipLaunchKernelGGL(K<3>, dim3(512), dim3(256), 0, s, a); } while (0)
-        if (p->env.on && p->gtao.on) BRMI_LAUNCH_SHADOWED(k_shade_ibl_ao_shadow);
-        else if (p->env.on) BRMI_LAUNCH_SHADOWED(k_shade_ibl_shadow);
-        else BRMI_LAUNCH_SHADOWED(k_shade_shadow);
-#undef BRMI_LAUNCH_SHADOWED
-        BRMI_LAUNCH_CHECK(p, "k_shade_shadow");
+    // one family's launches: the main one in its form for a shared or a whole chip, then the deferred pixels by class (coat, fuzz, both) -- only the variants some
+    // material of the scene can need
+    auto launch = [&](auto shared, auto alone, auto coat, auto fuzz, auto both, const char* what) -> int {
+        if (sharesChip) hipLaunchKernelGGL(shared, dim3(std::max(256u, p->shadeGridShared / share)), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(alone, dim3(std::max(256u, 8192u / share)), dim3(256), 0, s, a);
+        if (p->tables.hasCoat) hipLaunchKernelGGL(coat, dim3(512), dim3(256), 0, s, a);
+        if (p->tables.hasFuzz) hipLaunchKernelGGL(fuzz, dim3(512), dim3(256), 0, s, a);
+        if (p->tables.hasCoat && p->tables.hasFuzz) hipLaunchKernelGGL(both, dim3(512), dim3(256), 0, s, a);
+        BRMI_LAUNCH_CHECK(p, what);
         return BRMI_OK;
+    };
+    // brmi_set_shadows: each family with the shadow test in its light loop.  A bound environment (brmi_set_environment) selects the k_shade_ibl instantiations, with
+    // brmi_set_gtao's term the k_shade_ibl_ao ones (without an environment nothing reads the term); without either the launches are the ones they always were
+    if (p->shadows.on) {
+        if (p->env.on && p->gtao.on) return launch(k_shade_ibl_ao_shadow<0, BRMI_SHADE_WAVES>, k_shade_ibl_ao_shadow<0, BRMI_SHADE_WAVES_ALONE>, k_shade_ibl_ao_shadow<1>, k_shade_ibl_ao_shadow<2>, k_shade_ibl_ao_shadow<3>, "k_shade_shadow");
+        if (p->env.on) return launch(k_shade_ibl_shadow<0, BRMI_SHADE_WAVES>, k_shade_ibl_shadow<0, BRMI_SHADE_WAVES_ALONE>, k_shade_ibl_shadow<1>, k_shade_ibl_shadow<2>, k_shade_ibl_shadow<3>, "k_shade_shadow");
+        return launch(k_shade_shadow<0, BRMI_SHADE_WAVES>, k_shade_shadow<0, BRMI_SHADE_WAVES_ALONE>, k_shade_shadow<1>, k_shade_shadow<2>, k_shade_shadow<3>, "k_shade_shadow");
     }
-    if (p->env.on && p->gtao.on) {      // (without an environment nothing reads the term: the k_shade launches below)
-        if (sharesChip) hipLaunchKernelGGL((k_shade_ibl_ao<0, BRMI_SHADE_WAVES>), dim3(std::max(256u, p->shadeGridShared / share)), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((k_shade_ibl_ao<0, BRMI_SHADE_WAVES_ALONE>), dim3(std::max(256u, 8192u / share)), dim3(256), 0, s, a);
-        if (p->tables.hasCoat) hipLaunchKernelGGL(k_shade_ibl_ao<1>, dim3(512), dim3(256), 0, s, a);
-        if (p->tables.hasFuzz) hipLaunchKernelGGL(k_shade_ibl_ao<2>, dim3(512), dim3(256), 0, s, a);
-        if (p->tables.hasCoat && p->tables.hasFuzz) hipLaunchKernelGGL(k_shade_ibl_ao<3>, dim3(512), dim3(256), 0, s, a);
-        BRMI_LAUNCH_CHECK(p, "k_shade_ibl_ao");
-        return BRMI_OK;
-    }
-    if (p->env.on) {
-        if (sharesChip) hipLaunchKernelGGL((k_shade_ibl<0, BRMI_SHADE_WAVES>), dim3(std::max(256u, p->shadeGridShared / share)), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((k_shade_ibl<0, BRMI_SHADE_WAVES_ALONE>), dim3(std::max(256u, 8192u / share)), dim3(256), 0, s, a);
-        if (p->tables.hasCoat) hipLaunchKernelGGL(k_shade_ibl<1>, dim3(512), dim3(256), 0, s, a);
-        if (p->tables.hasFuzz) hipLaunchKernelGGL(k_shade_ibl<2>, dim3(512), dim3(256), 0, s, a);
-        if (p->tables.hasCoat && p->tables.hasFuzz) hipLaunchKernelGGL(k_shade_ibl<3>, dim3(512), dim3(256), 0, s, a);
-        BRMI_LAUNCH_CHECK(p, "k_shade_ibl");
-        return BRMI_OK;
-    }
-    if (sharesChip) hipLaunchKernelGGL((k_shade<0, BRMI_SHADE_WAVES>), dim3(std::max(256u, p->shadeGridShared / share)), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_shade<0, BRMI_SHADE_WAVES_ALONE>), dim3(std::max(256u, 8192u / share)), dim3(256), 0, s, a);
-    // deferred pixels by class: coat, fuzz, both -- only the variants some material of the scene can need
-    if (p->tables.hasCoat) hipLaunchKernelGGL(k_shade<1>, dim3(512), dim3(256), 0, s, a);
-    if (p->tables.hasFuzz) hipLaunchKernelGGL(k_shade<2>, dim3(512), dim3(256), 0, s, a);
-    if (p->tables.hasCoat && p->tables.hasFuzz) hipLaunchKernelGGL(k_shade<3>, dim3(512), dim3(256), 0, s, a);
-    BRMI_LAUNCH_CHECK(p, "k_shade");
-    return BRMI_OK;
+    if (p->env.on && p->gtao.on) return launch(k_shade_ibl_ao<0, BRMI_SHADE_WAVES>, k_shade_ibl_ao<0, BRMI_SHADE_WAVES_ALONE>, k_shade_ibl_ao<1>, k_shade_ibl_ao<2>, k_shade_ibl_ao<3>, "k_shade_ibl_ao");
+    if (p->env.on) return launch(k_shade_ibl<0, BRMI_SHADE_WAVES>, k_shade_ibl<0, BRMI_SHADE_WAVES_ALONE>, k_shade_ibl<1>, k_shade_ibl<2>, k_shade_ibl<3>, "k_shade_ibl");
+    return launch(k_shade<0, BRMI_SHADE_WAVES>, k_shade<0, BRMI_SHADE_WAVES_ALONE>, k_shade<1>, k_shade<2>, k_shade<3>, "k_shade");
 }
 
 // brmi_debug_ibl_lookup: the cube lookup as k_shade_ibl calls it, one lane per sample

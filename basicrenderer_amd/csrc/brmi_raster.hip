@@ -1495,13 +1495,13 @@ int launch_raster(brmi_pass* p, FrameCtx& ctx, uint32_t phase, hipStream_t s) {
     // draws the ones it cannot prove hidden in a late pass -- all inside this stage, before anything reads the phase-1 depth (k_retest_held)
     const bool hold = phase == 1 && p->holdThisFrame;
     if (hold) { a.drawList = p->wsPtr<uint32_t>(p->ws.drawList); a.countCounter = CNT_DRAW1; }
-    // round 6: triangles that reach very many bins are queued for k_raster_wide -- launched while the frames before had such triangles (host-mapped word 7: phase 1's
-    // count, stored by the plan; a frame or two old, and either way the same records)
-    const uint32_t lastWide = p->phase2FeedbackHost ? reinterpret_cast<volatile uint32_t*>(p->phase2FeedbackHost)[7] : 0u;
+    // round 6: triangles that reach very many bins are queued for k_raster_wide -- launched while the frames before had such triangles (phase 1's count, stored by
+    // the plan; a frame or two old, and either way the same records)
+    const uint32_t lastWide = p->feedback.last(FB_WIDE1, 0u);
     const bool wideOn = p->wideCapacity != 0u && lastWide >= std::max(1u, p->wideMinTriangles);
     a.wideQueue = wideOn ? p->wsPtr<WideTri>(p->ws.wideQueue) : nullptr; a.wideAlpha = p->wsPtr<AlphaRecord>(p->ws.wideAlpha); a.wideCapacity = p->wideCapacity;
     a.wideCounter = phase == 2 ? (uint32_t)CNT_WIDE2 : (uint32_t)CNT_WIDE1; a.wideEntries = p->wideEntries;
-    a.wideFeedback = (phase == 1 && p->phase2FeedbackDev) ? p->phase2FeedbackDev + 7 : nullptr;
+    a.wideFeedback = phase == 1 ? p->feedback.dev(FB_WIDE1) : nullptr;
     const dim3 wgrid(std::max(64u, std::min(8192u, lastWide * 8u)));      // eight single-wave workgroups per queued triangle (WIDE_SHARES)
     // (the interleaved partition's surface rows are not the frame rows the boxes are in: there the second build redoes everything)
     a.chainDirty = (phase == 2 && p->stripes.count <= 1u) ? p->wsPtr<uint8_t>(p->ws.chainDirty) : nullptr; a.chainBlocksX = (p->cfg.width + 31u) / 32u;
@@ -1535,8 +1535,7 @@ int launch_raster(brmi_pass* p, FrameCtx& ctx, uint32_t phase, hipStream_t s) {
     // wave that finds nothing still has to find a slot -- 200 VGPRs for k_raster<true>, 66 KB of LDS for a k_raster_bins<true> workgroup -- and the three
     // phase-2 launches of a still camera cost the San-Miguel-class frame ~150 us of its geometry chain in flight (kernel stats: k_raster<true> 61 us,
     // k_raster_overflow<true> 53, k_raster_bins<true> 150 per launch on average, phase 1 and 2 alike).
-    uint32_t hint2 = 0xFFFFFFFFu;
-    if (phase == 2 && p->phase2FeedbackHost) hint2 = *reinterpret_cast<volatile uint32_t*>(p->phase2FeedbackHost);
+    const uint32_t hint2 = phase == 2 ? p->feedback.last(FB_PLACED2, 0xFFFFFFFFu) : 0xFFFFFFFFu;
     auto pow2_at_least = [](uint32_t v) { uint32_t r = 1; while (r < v && r < (1u << 30)) r <<= 1; return r; };
     const bool sized2 = hint2 < 128u;
     const dim3 bgrid(phase == 2 ? (sized2 ? std::max(16u, std::min(256u, pow2_at_least(hint2 * 2u))) : std::min(p->binGrid, 256u)) : p->binGrid);
@@ -1547,67 +1546,69 @@ int launch_raster(brmi_pass* p, FrameCtx& ctx, uint32_t phase, hipStream_t s) {
     // limit the three launches pay (1,000 clusters: raster2 0.068 against 0.121 ms).  Either way the same keys.
     // (not in scenes with alpha-tested materials: a tested pixel costs three times as much through the global chain as in a bin, and the
     // San-Miguel-class camera path got 9 % slower with 19 phase-2 clusters per frame)
-    const bool direct2 = phase == 2 && !p->tables.hasAlphaTest && p->phase2FeedbackHost && *reinterpret_cast<volatile uint32_t*>(p->phase2FeedbackHost) <= p->phase2DirectMax && p->phase2DirectMax != 0u;
+    // (never without a block: dev() is null then)
+    const bool direct2 = phase == 2 && !p->tables.hasAlphaTest && p->feedback.dev(FB_PLACED2) && hint2 <= p->phase2DirectMax && p->phase2DirectMax != 0u;
     if (direct2) a.bigTriArea = a.bigTriAreaAlpha = a.bigTriAreaDense = 0x3FFFFFFF;
     // phase 2 rarely has more than a handful of clusters: 2048 workgroups (the kernel strides; two waves per SIMD) start and retire a little
     // faster than 8192 that find nothing (-3 us per frame)
     constexpr uint32_t grid2 = 2048;
     const dim3 rgrid(phase == 2 ? std::min(p->rasterGrid, sized2 ? std::max(128u, std::min(grid2, pow2_at_least(hint2 * 16u))) : grid2) : p->rasterGrid);
     const dim3 ogrid(phase == 2 && sized2 ? std::max(2u, std::min(129u, hint2 / 4u + 2u)) : 129u);      // (block 0 plans the bins launch; the others walk the overflow queues)
-    if (p->tables.hasAlphaTest) {
-        hipLaunchKernelGGL(k_raster<true>, rgrid, dim3(64), a.tableCells * 4u, s, a);
-        if (!direct2 && wideOn) hipLaunchKernelGGL(k_raster_wide<true>, wgrid, dim3(64), 0, s, a);
-        if (!direct2) hipLaunchKernelGGL(k_raster_overflow<true>, ogrid, dim3(256), 0, s, a);
-        if (!direct2) hipLaunchKernelGGL(k_raster_bins<true>, bgrid, dim3(BRMI_BIN_THREADS), 0, s, a);
-    } else {
+    // One pass's launches for `ra`: k_raster (unless the lean launches below stood in for it), then -- unless `direct` sent every triangle through the row re-deal of that
+    // launch -- the wide pass, the overflow walk whose block 0 plans the bins, and the bins.  og counts 256-thread workgroups; surfaces of more than 4096 bins without
+    // alpha-tested materials walk the queues with 1024-thread ones, a quarter as many behind the planning block.
+    auto chain = [&](auto alpha, const RasterArgs& ra, bool rasterLaunched, dim3 rg, dim3 og, dim3 bg, bool direct) {
+        constexpr bool ALPHA = decltype(alpha)::value;
+        if (!rasterLaunched) hipLaunchKernelGGL(k_raster<ALPHA>, rg, dim3(64), ra.tableCells * 4u, s, ra);
+        if (direct) return;
+        if (wideOn) hipLaunchKernelGGL(k_raster_wide<ALPHA>, wgrid, dim3(64), 0, s, ra);
+        if (!ALPHA && p->binsX * p->binsY > 4096u) hipLaunchKernelGGL((k_raster_overflow<false, 1024>), dim3((og.x - 1u + 3u) / 4u + 1u), dim3(1024), 0, s, ra);
+        else hipLaunchKernelGGL(k_raster_overflow<ALPHA>, og, dim3(256), 0, s, ra);
+        hipLaunchKernelGGL(k_raster_bins<ALPHA>, bg, dim3(BRMI_BIN_THREADS), 0, s, ra);
+    };
+    if (p->tables.hasAlphaTest) chain(std::true_type{}, a, false, rgrid, ogrid, bgrid, direct2);
+    else {
         // round 6: the lean form for frames of very many clusters (k_raster<false, true>), the general launch behind it for what it leaves.  Decided from what the host last
-        // saw of such launches (host-mapped words 8 / 9: the main launch's cluster count, the general launch's; a frame or two old -- either way the same keys).
-        volatile uint32_t* fb = p->phase2FeedbackHost;
+        // saw of such launches (the main launch's cluster count, the general launch's; a frame or two old -- either way the same keys).
+        uint32_t* const leanFeedback = (phase == 1 && p->leanMinClusters != 0u && p->stripes.count <= 1u) ? p->feedback.dev(FB_LEAN_COUNT) : nullptr;      // (null also without a block)
         bool lean = false;
-        if (phase == 1 && fb && p->leanMinClusters != 0u && p->stripes.count <= 1u) {
-            const uint32_t lastCount = fb[8], lastGeneral = fb[9];
+        if (leanFeedback) {
+            const uint32_t lastCount = p->feedback.last(FB_LEAN_COUNT, 0u), lastGeneral = p->feedback.last(FB_GENERAL_COUNT, 0u);
             if (p->leanActive) {
                 if (lastCount < p->leanMinClusters) p->leanActive = false;
                 else if ((uint64_t)lastGeneral * 100u > (uint64_t)lastCount * p->leanMaxGeneralPct) { p->leanActive = false; p->leanRetryIn = 64u; }
             } else if (p->leanRetryIn != 0u) p->leanRetryIn--;
-            else if (lastCount >= p->leanMinClusters) { p->leanActive = true; fb[9] = 0u; }
+            else if (lastCount >= p->leanMinClusters) { p->leanActive = true; p->feedback.store(FB_GENERAL_COUNT, 0u); }
             lean = p->leanActive;
-            a.countFeedback = p->phase2FeedbackDev + 8;
+            a.countFeedback = leanFeedback;
         }
         if (phase == 1) p->leanLastLaunch = lean;
         if (lean) {
-            a.generalList = p->wsPtr<uint32_t>(p->ws.generalList); a.generalCounter = CNT_GENERAL1; a.generalFeedback = p->phase2FeedbackDev + 9;
+            a.generalList = p->wsPtr<uint32_t>(p->ws.generalList); a.generalCounter = CNT_GENERAL1; a.generalFeedback = p->feedback.dev(FB_GENERAL_COUNT);
             a.bigQueue = p->wsPtr<WideTri>(p->ws.bigQueue); a.bigRuns = p->wsPtr<uint2>(p->ws.bigRuns); a.bigCapacity = p->leanQueue / 64u; a.bigCounter = CNT_BIG1;
             hipLaunchKernelGGL((k_raster<false, true>), dim3(p->leanGrid), dim3(64), 0, s, a);
             hipLaunchKernelGGL(k_raster_emit, dim3(p->leanEmitGrid), dim3(64), a.tableCells * 4u, s, a);
             RasterArgs g = a;
-            g.drawList = a.generalList; g.firstCounter = 0xFFFFFFFFu; g.countCounter = CNT_GENERAL1; g.countFeedback = p->phase2FeedbackDev + 9;
-            const dim3 ggrid(std::min(p->rasterGrid, std::max(128u, pow2_at_least(std::min((uint32_t)fb[9], 1u << 20) * 16u))));
+            g.drawList = a.generalList; g.firstCounter = 0xFFFFFFFFu; g.countCounter = CNT_GENERAL1; g.countFeedback = p->feedback.dev(FB_GENERAL_COUNT);
+            const dim3 ggrid(std::min(p->rasterGrid, std::max(128u, pow2_at_least(std::min(p->feedback.last(FB_GENERAL_COUNT, 0u), 1u << 20) * 16u))));
             hipLaunchKernelGGL(k_raster<false>, ggrid, dim3(64), g.tableCells * 4u, s, g);
-        } else
-        hipLaunchKernelGGL(k_raster<false>, rgrid, dim3(64), a.tableCells * 4u, s, a);
-        if (!direct2 && wideOn) hipLaunchKernelGGL(k_raster_wide<false>, wgrid, dim3(64), 0, s, a);
-        if (!direct2) {
-            if (p->binsX * p->binsY > 4096u) hipLaunchKernelGGL((k_raster_overflow<false, 1024>), dim3((ogrid.x - 1u + 3u) / 4u + 1u), dim3(1024), 0, s, a);
-            else hipLaunchKernelGGL(k_raster_overflow<false>, ogrid, dim3(256), 0, s, a);
         }
-        if (!direct2) hipLaunchKernelGGL(k_raster_bins<false>, bgrid, dim3(BRMI_BIN_THREADS), 0, s, a);
+        chain(std::false_type{}, a, lean, rgrid, ogrid, bgrid, direct2);
     }
     BRMI_LAUNCH_CHECK(p, "k_raster");
     if (hold) {
         // the chain of the keys the draw list left (LinearDepthCopyPass1 + LinearDepthDownsamplePass1's work, done here; the frame's own build after this stage then only
         // redoes the blocks the late pass touched: launch_hzb)
         if (int rc = launch_hzb(p, ctx, s, ChainBuild::InRaster)) return rc;
-        volatile uint32_t* fb = p->phase2FeedbackHost;      // words 5 / 6: the late and the held count of the frames before (no wait; any value gives the same keys)
-        const uint32_t lastLate = fb ? fb[5] : 0u, lastHeld = fb ? fb[6] : 0xFFFFFFFFu;
+        const uint32_t lastLate = p->feedback.last(FB_LATE, 0u), lastHeld = p->feedback.last(FB_HELD, 0xFFFFFFFFu);      // (of the frames before; no wait, any value gives the same keys)
         RetestArgs r;
         r.held = p->wsPtr<HeldRecord>(p->ws.heldRecords); r.boxes = p->wsPtr<MeshletBox>(p->ws.meshletBoxes); r.objConst = a.objConst; r.viewRasterInfo = p->scene.viewRasterInfo;
         r.hzb = p->hzbDesc(); r.visW = a.visW; r.visH = a.visH; r.capacity = p->cfg.maxVisibleClusters; r.maxTexels = p->retestMaxTexels; r.bandY0 = p->bandY0; r.bandY1 = p->bandY1;
-        r.counters = p->counters(); r.lateList = p->wsPtr<uint32_t>(p->ws.lateList); r.heldFeedback = p->phase2FeedbackDev ? p->phase2FeedbackDev + 6 : nullptr;
+        r.counters = p->counters(); r.lateList = p->wsPtr<uint32_t>(p->ws.lateList); r.heldFeedback = p->feedback.dev(FB_HELD);
         const uint32_t tgrid = std::max(16u, std::min(4096u, pow2_at_least(std::min(lastHeld, p->cfg.maxVisibleClusters) / 256u + 1u)));
         hipLaunchKernelGGL(k_retest_held, dim3(tgrid), dim3(256), 0, s, r);
         RasterArgs l = a;
-        l.drawList = r.lateList; l.countCounter = CNT_LATE1; l.countFeedback = p->phase2FeedbackDev ? p->phase2FeedbackDev + 5 : nullptr;
+        l.drawList = r.lateList; l.countCounter = CNT_LATE1; l.countFeedback = p->feedback.dev(FB_LATE);
         l.wideCounter = CNT_WIDE1B; l.wideFeedback = nullptr;
         // what the late pass draws changes the depth under it: it records the 32 x 32 px blocks its triangles may touch, like phase 2
         l.chainDirty = p->wsPtr<uint8_t>(p->ws.chainDirty); l.chainBlocksX = (p->cfg.width + 31u) / 32u;
@@ -1617,19 +1618,8 @@ int launch_raster(brmi_pass* p, FrameCtx& ctx, uint32_t phase, hipStream_t s) {
         const bool directLate = lastLate <= (p->tables.hasAlphaTest ? 0u : p->lateDirectMax);
         if (directLate) l.bigTriArea = l.bigTriAreaAlpha = l.bigTriAreaDense = 0x3FFFFFFF;
         const dim3 lgrid(std::min(p->rasterGrid, std::max(128u, pow2_at_least(std::min(lastLate, 1u << 20) * 16u))));
-        if (p->tables.hasAlphaTest) {
-            hipLaunchKernelGGL(k_raster<true>, lgrid, dim3(64), l.tableCells * 4u, s, l);
-            if (!directLate && wideOn) hipLaunchKernelGGL(k_raster_wide<true>, wgrid, dim3(64), 0, s, l);
-            if (!directLate) { hipLaunchKernelGGL(k_raster_overflow<true>, dim3(129), dim3(256), 0, s, l); hipLaunchKernelGGL(k_raster_bins<true>, dim3(p->binGrid), dim3(BRMI_BIN_THREADS), 0, s, l); }
-        } else {
-            hipLaunchKernelGGL(k_raster<false>, lgrid, dim3(64), l.tableCells * 4u, s, l);
-            if (!directLate && wideOn) hipLaunchKernelGGL(k_raster_wide<false>, wgrid, dim3(64), 0, s, l);
-            if (!directLate) {
-                if (p->binsX * p->binsY > 4096u) hipLaunchKernelGGL((k_raster_overflow<false, 1024>), dim3(33), dim3(1024), 0, s, l);
-                else hipLaunchKernelGGL(k_raster_overflow<false>, dim3(129), dim3(256), 0, s, l);
-                hipLaunchKernelGGL(k_raster_bins<false>, dim3(p->binGrid), dim3(BRMI_BIN_THREADS), 0, s, l);
-            }
-        }
+        if (p->tables.hasAlphaTest) chain(std::true_type{}, l, false, lgrid, dim3(129), dim3(p->binGrid), directLate);
+        else chain(std::false_type{}, l, false, lgrid, dim3(129), dim3(p->binGrid), directLate);
         BRMI_LAUNCH_CHECK(p, "late raster pass");
     }
     return BRMI_OK;

@@ -31,7 +31,7 @@ struct GBufferArgs {
     const m4* frameConst; const float* objConst;
     const ClusterSetup* setup; ResolveVertex* verts; ResolveTriangle* tris; uint32_t vertCapacity, triCapacity;
     MaterialWords* matWords;
-    uint32_t* hostFeedback;        // host-mapped words (brmi_pass::ensureFeedback) or null
+    uint32_t* hostFeedback;        // the host-mapped block (HostFeedback::devBlock) or null: FB_RESOLVE_INLINE is stored here
     const ClusterUv* clusterUv; float2* uvs;      // textured scenes: where the UV sets of every visible cluster live, decoded texcoords of the arena's vertices
     uint32_t uvSets;                              // sets the materials of the scene address (1 unless one names a set > 0): uvs holds [set][vertCapacity]
     uint32_t* colors;                             // scenes with vertex colours: the RGBA8 colour of the arena's vertices
@@ -107,7 +107,7 @@ BRMI_DEV void resolve_setup_cluster(const GBufferArgs& a, uint32_t c, uint32_t l
 BRMI_DEV void resolve_setup_feedback(const GBufferArgs& a, uint32_t lane) {
     if (blockIdx.x == 0u && lane == 0u && a.hostFeedback && a.setupPart != 1u) {
         const uint64_t tris = (uint64_t)a.counters[CNT_SUM_VERTS_HI];
-        __hip_atomic_store(a.hostFeedback + 1, tris * a.inlineRatio > a.pixelCount ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(a.hostFeedback + FB_RESOLVE_INLINE, tris * a.inlineRatio > a.pixelCount ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 __global__ void __launch_bounds__(64) k_resolve_setup(GBufferArgs a) {
@@ -324,7 +324,7 @@ BRMI_DEV void gbuffer_body(const GBufferArgs& a, const Epi& epi) {
     const brmi_scene_buffers& sc = a.sc;
     if (a.variantSelect != 0u && (a.counters[CNT_RESOLVE_SPILL] != 0u) != (a.variantSelect == 2u)) return;     // the other variant's frame
     if (INLINE_TABLES && a.hostFeedback && blockIdx.x == 0u && threadIdx.x == 0u)      // a frame without the setup launch: this kernel tells the host whether frames like this one are still of that kind
-        __hip_atomic_store(a.hostFeedback + 1, (uint64_t)a.counters[CNT_SUM_VERTS_HI] * a.inlineRatio > a.pixelCount ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(a.hostFeedback + FB_RESOLVE_INLINE, (uint64_t)a.counters[CNT_SUM_VERTS_HI] * a.inlineRatio > a.pixelCount ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __shared__ float texelTables[TEXTURED ? 512 : 1];          // code -> float: unorm, sRGB decode
     if (TEXTURED) { stage_texel_tables(texelTables, sc.srgbToLinear, threadIdx.x, 256u); __syncthreads(); }
     TexelTables tb; tb.t = texelTables;
@@ -657,14 +657,14 @@ static GBufferArgs gbuffer_args_of(brmi_pass* p) {
 uint32_t resolve_inline_ratio(const brmi_pass* p) { return (p->tables.hasTextures || p->tables.hasVertexColors) ? 2u : 4u; }
 bool resolve_inline_frame(brmi_pass* p) {
     if (p->resolveInlineMode >= 0) return p->resolveInlineMode != 0;
-    return (uint64_t)p->tables.totalBits * BRMI_MESHLET_MAX_TRIS * resolve_inline_ratio(p) > p->bandPixelCount && p->ensureFeedback() && reinterpret_cast<volatile uint32_t*>(p->phase2FeedbackHost)[1] != 0u;
+    return (uint64_t)p->tables.totalBits * BRMI_MESHLET_MAX_TRIS * resolve_inline_ratio(p) > p->bandPixelCount && p->feedback.ensure() && p->feedback.last(FB_RESOLVE_INLINE, 0u) != 0u;
 }
 int launch_resolve_setup(brmi_pass* p, FrameCtx& ctx, hipStream_t s, uint32_t part) {
     if (int rc = ensure_frame_constants(p, ctx, s)) return rc;
     ctx.resolveTableParts |= part ? part : 3u;
     if (p->inlineResolve) return BRMI_OK;      // (the compaction marked every cluster "no tables")
     GBufferArgs a = gbuffer_args_of(p);
-    a.hostFeedback = p->ensureFeedback() ? p->phase2FeedbackDev : nullptr;
+    a.hostFeedback = p->feedback.ensure() ? p->feedback.devBlock() : nullptr;
     a.setupPart = part;
     // (brmi_execute_split: phase-1 clusters beside the rasteriser on the shading stream, phase-2 clusters -- usually a handful -- at the end of the geometry half)
     const dim3 grid(part == 2u ? 512 : 8192);
@@ -696,7 +696,7 @@ int launch_gbuffer(brmi_pass* p, FrameCtx& ctx, hipStream_t s) {
     // launch against the two-waves-per-SIMD fallback variant on frames that do not need it: San-Miguel-class 4K 1.04 -> 0.98 ms).
     auto launch = [&](auto leanKernel, auto fallbackKernel) {
         if (p->inlineResolve) {      // every cluster without tables: the in-place form alone
-            a.variantSelect = 0u; a.hostFeedback = p->ensureFeedback() ? p->phase2FeedbackDev : nullptr;
+            a.variantSelect = 0u; a.hostFeedback = p->feedback.ensure() ? p->feedback.devBlock() : nullptr;
             hipLaunchKernelGGL(fallbackKernel, dim3(8192), dim3(256), 0, s, a);
             return;
         }
