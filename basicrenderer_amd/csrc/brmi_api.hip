@@ -274,6 +274,7 @@ int brmi_create(const brmi_config* cfg, brmi_pass** out) {
     p->resolveInlineMode = (int)tuning("resolve_inline", -1);
     p->wideCapacity = (uint32_t)std::min(1l << 20, std::max(0l, tuning("wide_capacity", p->wideCapacity)));
     p->wideMinTriangles = (uint32_t)std::max(0l, tuning("wide_min_triangles", p->wideMinTriangles));
+    p->rasterSlim = (int)std::max(-1l, std::min(1l, tuning("raster_slim", -1)));      // 0 | 1: today's or the slim shape of k_raster on every frame; unset (or -1): launch_raster picks
     p->leanMinClusters = (uint32_t)std::max(0l, tuning("lean_min_clusters", p->leanMinClusters));
     if (p->leanMinClusters > cfg->maxVisibleClusters) p->leanMinClusters = 0u;      // a pass whose list cannot get that long never runs the lean rasteriser: no queue in its workspace (104 MB)
     p->leanMaxGeneralPct = (uint32_t)std::max(0l, std::min(100l, tuning("lean_max_general_pct", p->leanMaxGeneralPct)));
@@ -1158,6 +1159,12 @@ int brmi_debug_lean_clusters(brmi_pass* p, uint32_t out[4]) {
     BRMI_HIP(p, hipMemcpy(heads, p->counters() + CNT_BIG1, sizeof(heads), hipMemcpyDeviceToHost));
     out[0] = p->leanLastLaunch ? 1u : 0u; out[1] = c; out[2] = out[3] = 0u;
     for (uint32_t s = 0; s < 64u; s++) { out[2] += heads[s * 32u]; out[3] += heads[s * 32u + 1u]; }
+    return BRMI_OK;
+}
+
+int brmi_debug_raster_shape(brmi_pass* p, uint32_t* slim) {
+    if (!p || !slim || !p->setupDone) return BRMI_ERR_INVALID;
+    *slim = p->slimLastLaunch ? 1u : 0u;
     return BRMI_OK;
 }
 

@@ -233,6 +233,8 @@ BRMI_DEV m4 load_bone_skin_matrix(const float* skinningMatrices, uint32_t slot, 
     return r;
 }
 // BuildSkinMatrix: w0*M0 + w1*M1 + ... + w7*M7, left to right
+// IN_FLIGHT < 8: the bone matrices are requested that many at a time (a caller short of registers: eight matrices are 128 values); the sum and its order are the same
+template <int IN_FLIGHT = 8>
 BRMI_DEV m4 build_skin_matrix(const float* skinningMatrices, uint32_t slot, const uint32_t* joints, const float* weights) {
     m4 r;
     if (slot == 0xFFFFFFFFu || skinningMatrices == nullptr) {
@@ -244,6 +246,7 @@ BRMI_DEV m4 build_skin_matrix(const float* skinningMatrices, uint32_t slot, cons
     }
 #pragma unroll
     for (int k = 0; k < 8; k++) {
+        if (IN_FLIGHT < 8 && k != 0 && k % IN_FLIGHT == 0) __builtin_amdgcn_sched_barrier(0);
         const m4 b = load_bone_skin_matrix(skinningMatrices, slot, joints[k]);
 #pragma unroll
         for (int i = 0; i < 4; i++)

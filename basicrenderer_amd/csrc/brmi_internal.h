@@ -358,6 +358,9 @@ struct brmi_pass {
                                      // triangles than pixels (resolve_inline_frame)
     // the lean rasteriser's controller, from frame to frame: written and read by phase 1 of launch_raster alone
     bool leanActive = false, leanLastLaunch = false; uint32_t leanRetryIn = 0;
+    // the register shape of the opaque direct rasteriser (brmi_raster.hip, k_raster<false, false> / k_raster_slim): BRMI_TUNING raster_slim=0|1 forces today's or the slim one,
+    // auto (-1) leaves it to launch_raster (slim on a frame of two streams); slimLastLaunch: a launch of the last frame's phase 1 (main, general-list or late) was k_raster_slim (brmi_debug_raster_shape)
+    int rasterSlim = -1; bool slimLastLaunch = false;
     // Round 6, the draw list: whether this pass holds clusters back (brmi_raster.hip)
     bool holdEnabled = false;        // the pass can hold clusters back: occlusion culling on, no band / interleaved partition, boxes available (BRMI_TUNING hold_clusters=0: off)
     uint32_t holdMinClusters = 16384; // hold only on frames whose last known visible-cluster count is at least this (BRMI_TUNING hold_min_clusters): below it the re-test, the late

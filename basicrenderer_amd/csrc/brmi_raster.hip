@@ -300,9 +300,12 @@ BRMI_DEV void bin_append(const RasterArgs& a, const float* unorm, const BinRecor
 #ifndef BRMI_RASTER_LEAN_WAVES
 #define BRMI_RASTER_LEAN_WAVES 6
 #endif
-template <bool ALPHA, bool LEAN = false>
-__global__ void __launch_bounds__(64, LEAN ? BRMI_RASTER_LEAN_WAVES : (ALPHA ? BRMI_RASTER_ALPHA_WAVES : BRMI_RASTER_WAVES)) k_raster(RasterArgs a) {
+// SLIM: the second register shape of the opaque direct rasteriser (k_raster_slim below; a kernel of its own name, so that k_raster<false, false> keeps its name in traces and tables), for frames that share the chip with another frame's shading half.
+// Same vertices, triangles, pixels and records; what differs is how much a wave requests ahead and what it carries from stage to stage (marked SLIM in the body).
+template <bool ALPHA, bool LEAN, bool SLIM>
+BRMI_DEV void raster_clusters(RasterArgs a) {
     static_assert(!(ALPHA && LEAN), "the lean form has no alpha test");
+    static_assert(!SLIM || (!ALPHA && !LEAN), "the slim shape is the opaque direct rasteriser's");
     // (one wave per workgroup: LDS hand-offs between its lanes need wave_lds_sync() only.  __syncthreads() also waits for every global store
     // and atomic the wave has in flight -- the record stores and the small boxes' atomic-mins: a memory round trip per hand-off.)
     __shared__ float sx[BRMI_MESHLET_MAX_VERTS], sy[BRMI_MESHLET_MAX_VERTS], sd[BRMI_MESHLET_MAX_VERTS];
@@ -391,7 +394,8 @@ __global__ void __launch_bounds__(64, LEAN ? BRMI_RASTER_LEAN_WAVES : (ALPHA ? B
         // front of every pass's setup (15-27 % of the kernel's wave-cycles)
         uint32_t pi0[2] = {0u, 0u}, pi1[2] = {0u, 0u}, pi2[2] = {0u, 0u};
 #pragma unroll
-        for (uint32_t k = 0; k < 2u; k++) {
+        // (SLIM: six registers held across the vertex stage for a fetch that bought no time alone, DESIGN.md 4.3b: each pass requests its own at its setup)
+        for (uint32_t k = 0; k < (SLIM ? 0u : 2u); k++) {
             const uint32_t t = passLo + k * 64u + lane;
             if (passLo + k * 64u < passHi && t < triCount) { pi0[k] = triBase[t * 3u]; pi1[k] = triBase[t * 3u + 1u]; pi2[k] = triBase[t * 3u + 2u]; }
         }
@@ -404,8 +408,12 @@ __global__ void __launch_bounds__(64, LEAN ? BRMI_RASTER_LEAN_WAVES : (ALPHA ? B
         if (alphaCluster) { cu = a.clusterUv[clusterIndex]; amat = a.alphaMats[cs.materialDataIndex]; }
 
         // vertex stage -> LDS (softwareRaster.hlsl:339-387)
+        // (SLIM: the lane index behind an opaque copy: what derives from it -- the byte offsets of the position and skinning fetches -- is computed here, per cluster, instead
+        // of being carried from the kernel's prologue through every loop)
+        uint32_t vlane = lane;
+        if (SLIM) asm volatile("" : "+v"(vlane));
         if (!toGeneral)
-        for (uint32_t v = lane; v < vertCount; v += 64) {
+        for (uint32_t v = vlane; v < vertCount; v += 64) {
             f3 lp{0.0f, 0.0f, 0.0f};
             if (posFormat == BRMI_POSITION_FORMAT_FLOAT3) {
                 const float* pp = reinterpret_cast<const float*>(posBase + v * 12u);
@@ -414,7 +422,7 @@ __global__ void __launch_bounds__(64, LEAN ? BRMI_RASTER_LEAN_WAVES : (ALPHA ? B
             if (skinVerts) {
                 uint32_t joints[8]; float weights[8];
                 load_skin_influences(cs.nrmBase + cs.jointDelta + v * 32u, (cs.counts & BRMI_CS_WEIGHTS) ? cs.nrmBase + cs.weightDelta + v * 32u : nullptr, joints, weights);
-                lp = xyz(mul_point(lp, build_skin_matrix(sc.skinningMatrices, skinSlot, joints, weights)));
+                lp = xyz(mul_point(lp, build_skin_matrix<SLIM ? 2 : 8>(sc.skinningMatrices, skinSlot, joints, weights)));      // (SLIM: two bone matrices in flight, not as many as fit)
             }
             const f4 lp4{lp.x, lp.y, lp.z, 1.0f};
             const f4 clip = mul_vm(lp4, mvp);
@@ -438,6 +446,7 @@ __global__ void __launch_bounds__(64, LEAN ? BRMI_RASTER_LEAN_WAVES : (ALPHA ? B
             if (active) {
                 const uint32_t pk = (waveBase - passLo) >> 6;
                 uint32_t i0 = pk ? pi0[1] : pi0[0], i1 = pk ? pi1[1] : pi1[0], i2 = pk ? pi2[1] : pi2[0];
+                if (SLIM) { i0 = triBase[t * 3u]; i1 = triBase[t * 3u + 1u]; i2 = triBase[t * 3u + 2u]; }
                 if (reverseWinding) { const uint32_t tmp = i1; i1 = i2; i2 = tmp; }
                 if (alphaCluster) { arec.tri = AlphaTri{siw[i0], siw[i1], siw[i2], f2{su[i0], sv[i0]}, f2{su[i1], sv[i1]}, f2{su[i2], sv[i2]}}; arec.materialDataIndex = cs.materialDataIndex; }
                 const float s0x = sx[i0], s0y = sy[i0], s1x = sx[i1], s1y = sy[i1], s2x = sx[i2], s2y = sy[i2];
@@ -771,12 +780,14 @@ __global__ void __launch_bounds__(64, LEAN ? BRMI_RASTER_LEAN_WAVES : (ALPHA ? B
                     r.sb0 = sb0; r.sb1 = sb1; r.dx_b0 = c_dx0; r.dx_b1 = c_dx1; r.dy_b0 = c_dy0; r.dy_b1 = c_dy1; r.d0 = c_d0; r.d1 = c_d1; r.d2 = c_d2; r.pad0 = 0; r.pad1 = alphaCluster ? 1u : 0u;
                     // all the band's bin slots are requested before the first one is used: the atomics overlap instead of costing one
                     // round trip per strip (a full-width triangle touches 15-30 strips)
-                    for (int st0 = c_strip0; st0 <= c_strip1; st0 += 8) {
-                        uint32_t slots[8];
+                    // (SLIM: four at a time)
+                    constexpr int SLOTS = SLIM ? 4 : 8;
+                    for (int st0 = c_strip0; st0 <= c_strip1; st0 += SLOTS) {
+                        uint32_t slots[SLOTS];
 #pragma unroll
-                        for (int k = 0; k < 8; k++) slots[k] = (st0 + k <= c_strip1) ? atomicAdd(&a.binCounts[(size_t)(vb * a.binsX + (uint32_t)(st0 + k)) * BIN_COUNT_STRIDE], 1u) : 0u;
+                        for (int k = 0; k < SLOTS; k++) slots[k] = (st0 + k <= c_strip1) ? atomicAdd(&a.binCounts[(size_t)(vb * a.binsX + (uint32_t)(st0 + k)) * BIN_COUNT_STRIDE], 1u) : 0u;
 #pragma unroll
-                        for (int k = 0; k < 8; k++) if (st0 + k <= c_strip1) bin_store(a, unormT, r, c_arec, (uint32_t)(st0 + k), vb, slots[k]);
+                        for (int k = 0; k < SLOTS; k++) if (st0 + k <= c_strip1) bin_store(a, unormT, r, c_arec, (uint32_t)(st0 + k), vb, slots[k]);
                     }
                 }
             }
@@ -786,6 +797,13 @@ __global__ void __launch_bounds__(64, LEAN ? BRMI_RASTER_LEAN_WAVES : (ALPHA ? B
     }
     if (ALPHA && rqTail != rqHead) rq_drain(rqTail - rqHead);
 }
+template <bool ALPHA, bool LEAN = false>
+__global__ void __launch_bounds__(64, LEAN ? BRMI_RASTER_LEAN_WAVES : (ALPHA ? BRMI_RASTER_ALPHA_WAVES : BRMI_RASTER_WAVES)) k_raster(RasterArgs a) { raster_clusters<ALPHA, LEAN, false>(a); }
+// The slim shape: at most 104 VGPRs (AGPRs included), no scratch.  104 = 512 - 3 x 136: what three waves of the in-flight k_shade<0, 3> (pinned at 136 registers,
+// brmi_light.hip) leave of a SIMD's register file, so that a wave of this kernel starts beside them instead of waiting for one of them to retire.
+// (amdgpu_num_vgpr counts architectural registers; on gfx90a and later, where VGPRs and AGPRs are one file, the compiler doubles the figure into the budget of both, and a
+// kernel without AGPRs gets all of it as VGPRs: 52 states the bound of 104.  profiles/geometry_resources.md records what the compiler reports.)
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(52))) k_raster_slim(RasterArgs a) { raster_clusters<false, false, true>(a); }
 
 // The lean rasteriser's binned triangles (RasterArgs::bigQueue), 64 queue entries per wave and step: the record emission of k_raster on its own -- per-bin counts in
 // the LDS window, one reservation per bin and wave, slots handed out from LDS; triangles of more entries than the window rule allows are emitted by the whole wave, or
@@ -1554,12 +1572,20 @@ int launch_raster(brmi_pass* p, FrameCtx& ctx, uint32_t phase, hipStream_t s) {
     constexpr uint32_t grid2 = 2048;
     const dim3 rgrid(phase == 2 ? std::min(p->rasterGrid, sized2 ? std::max(128u, std::min(grid2, pow2_at_least(hint2 * 16u))) : grid2) : p->rasterGrid);
     const dim3 ogrid(phase == 2 && sized2 ? std::max(2u, std::min(129u, hint2 / 4u + 2u)) : 129u);      // (block 0 plans the bins launch; the others walk the overflow queues)
+    // The register shape of the opaque direct rasteriser (k_raster<false, false> / k_raster_slim): the slim one for a frame on two streams, whose geometry waves look for room beside
+    // another frame's shading waves; today's on one stream and from the stage entry point, where a wave has the SIMD's file to itself (as brmi_execute_split picks k_shade's
+    // variant).  BRMI_TUNING raster_slim=0|1 forces either on every frame.
+    const bool slim = !p->tables.hasAlphaTest && (p->rasterSlim < 0 ? ctx.twoStreams : p->rasterSlim != 0);
+    if (phase == 1) p->slimLastLaunch = false;      // (set where k_raster_slim is launched, below)
     // One pass's launches for `ra`: k_raster (unless the lean launches below stood in for it), then -- unless `direct` sent every triangle through the row re-deal of that
     // launch -- the wide pass, the overflow walk whose block 0 plans the bins, and the bins.  og counts 256-thread workgroups; surfaces of more than 4096 bins without
     // alpha-tested materials walk the queues with 1024-thread ones, a quarter as many behind the planning block.
     auto chain = [&](auto alpha, const RasterArgs& ra, bool rasterLaunched, dim3 rg, dim3 og, dim3 bg, bool direct) {
         constexpr bool ALPHA = decltype(alpha)::value;
-        if (!rasterLaunched) hipLaunchKernelGGL(k_raster<ALPHA>, rg, dim3(64), ra.tableCells * 4u, s, ra);
+        if (!rasterLaunched) {
+            if (!ALPHA && slim) { hipLaunchKernelGGL(k_raster_slim, rg, dim3(64), ra.tableCells * 4u, s, ra); if (phase == 1) p->slimLastLaunch = true; }
+            else hipLaunchKernelGGL(k_raster<ALPHA>, rg, dim3(64), ra.tableCells * 4u, s, ra);
+        }
         if (direct) return;
         if (wideOn) hipLaunchKernelGGL(k_raster_wide<ALPHA>, wgrid, dim3(64), 0, s, ra);
         if (!ALPHA && p->binsX * p->binsY > 4096u) hipLaunchKernelGGL((k_raster_overflow<false, 1024>), dim3((og.x - 1u + 3u) / 4u + 1u), dim3(1024), 0, s, ra);
@@ -1591,7 +1617,8 @@ int launch_raster(brmi_pass* p, FrameCtx& ctx, uint32_t phase, hipStream_t s) {
             RasterArgs g = a;
             g.drawList = a.generalList; g.firstCounter = 0xFFFFFFFFu; g.countCounter = CNT_GENERAL1; g.countFeedback = p->feedback.dev(FB_GENERAL_COUNT);
             const dim3 ggrid(std::min(p->rasterGrid, std::max(128u, pow2_at_least(std::min(p->feedback.last(FB_GENERAL_COUNT, 0u), 1u << 20) * 16u))));
-            hipLaunchKernelGGL(k_raster<false>, ggrid, dim3(64), g.tableCells * 4u, s, g);
+            if (slim) { hipLaunchKernelGGL(k_raster_slim, ggrid, dim3(64), g.tableCells * 4u, s, g); if (phase == 1) p->slimLastLaunch = true; }
+            else hipLaunchKernelGGL(k_raster<false>, ggrid, dim3(64), g.tableCells * 4u, s, g);
         }
         chain(std::false_type{}, a, lean, rgrid, ogrid, bgrid, direct2);
     }

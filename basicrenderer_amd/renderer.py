@@ -258,6 +258,12 @@ class VisibilityRenderer:
         self._check(self.lib.brmi_debug_lean_clusters(self._h, out), "brmi_debug_lean_clusters")
         return tuple(int(v) for v in out)
 
+    def raster_shape(self):
+        """1 if the last frame's phase 1 launched the slim register shape of the opaque direct rasteriser, 0 for the general one (brmi_debug_raster_shape)."""
+        out = capi.u32(0)
+        self._check(self.lib.brmi_debug_raster_shape(self._h, C.byref(out)), "brmi_debug_raster_shape")
+        return int(out.value)
+
     def wide_triangles(self):
         """(phase-1 draw pass, late pass, phase 2) counts of the last frame's triangles queued for the workgroup-wide record emission (brmi_debug_wide_triangles)."""
         out = (capi.u32 * 3)()

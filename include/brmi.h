@@ -567,6 +567,11 @@ int brmi_debug_wide_triangles(brmi_pass* pass, uint32_t out[3]);
  * triangles it queued for k_raster_emit (large enough for the bins) and the runs they were queued in (one per wave and pass; requested, so beyond a full queue's
  * capacity).  Waits for the device. */
 int brmi_debug_lean_clusters(brmi_pass* pass, uint32_t out[4]);
+/* The register shape of the opaque direct rasteriser the last frame's phase 1 launched: *slim = 1 when one of its k_raster launches (the main one, the
+ * one behind a lean launch, the late pass) was the slim shape (at most 104 VGPRs: a frame issued
+ * on two streams by brmi_execute_split, or BRMI_TUNING raster_slim=1), 0 for the general one (one stream, the stage entry point brmi_raster, raster_slim=0, or a scene
+ * with alpha-tested materials, which has no slim shape).  Host state only: does not wait for the device. */
+int brmi_debug_raster_shape(brmi_pass* pass, uint32_t* slim);
 /* One of the 64 stripes of that queue as the last frame left it: counts = {entries, runs} (clamped to the stripe's capacity); runs = {first entry, count} pairs,
  * entries = 96 B records (brmi_raster.hip, WideTri: a 64 B bin record of the triangle's first row, then yHi, band0, band1, strip0, strip1).  Either buffer may be null. */
 int brmi_debug_read_lean_queue(brmi_pass* pass, uint32_t stripe, uint32_t* runs, uint32_t maxRuns, void* entries, uint32_t maxEntries, uint32_t counts[2]);
