@@ -172,6 +172,21 @@ class DisplayBuffers(C.Structure):
                 ("blendedHdr", vp), ("blendedHdrBytes", u64)]
 
 
+class TemporalSettings(C.Structure):
+    """brmi_temporal_settings (include/brmi.h), 32 B."""
+    _fields_ = [("structSize", u32), ("blend", f32), ("phases", u32), ("reserved", u32 * 5)]
+
+
+class TemporalLayout(C.Structure):
+    """brmi_temporal_layout (include/brmi.h): the bytes of one history image, 16 B."""
+    _fields_ = [("historyBytes", u64), ("tilesX", u32), ("tilesY", u32)]
+
+
+class TemporalBuffers(C.Structure):
+    """brmi_temporal_buffers (include/brmi.h): the settings and the two caller-owned history images, 64 B."""
+    _fields_ = [("structSize", u32), ("reserved", u32), ("settings", TemporalSettings), ("history", vp * 2), ("historyBytes", u64)]
+
+
 TONEMAP_TYPES = {"reinhard": 0, "neutral": 1, "aces": 2, "lpm": 3, "none": 4}      # the reference's tonemapType setting; 4 is the switch's default
 GTAO_QUALITY = {"low": 0, "medium": 1, "high": 2, "ultra": 3}      # slices x steps: 1 x 2, 2 x 2, 3 x 3, 9 x 3
 
@@ -338,7 +353,9 @@ BRMI_EXPORTS = ["brmi_abi_version", "brmi_default_config", "brmi_create", "brmi_
                 "brmi_gtao_default_settings", "brmi_gtao_get_layout", "brmi_set_gtao", "brmi_gtao_prefilter", "brmi_gtao_main", "brmi_gtao_denoise",
                 "brmi_texmips_bytes", "brmi_texmips_build", "brmi_texmips_build_alpha",
                 "brmi_display_default_settings", "brmi_display_get_layout", "brmi_set_display", "brmi_display_exposure", "brmi_display_bloom", "brmi_display_resolve", "brmi_debug_display_bloom_pass", "brmi_debug_display_histogram",
-                "brmi_set_shadows", "brmi_shadow_capture", "brmi_debug_shadow"]
+                "brmi_set_shadows", "brmi_shadow_capture", "brmi_debug_shadow",
+                "brmi_temporal_default_settings", "brmi_temporal_get_layout", "brmi_set_temporal", "brmi_temporal_resolve", "brmi_temporal_reset", "brmi_temporal_state",
+                "brmi_debug_temporal_resolve"]
 
 
 def brmi_lib():
@@ -430,5 +447,14 @@ def brmi_lib():
             lib.brmi_set_shadows.argtypes = [vp, C.POINTER(ShadowBuffers)]
             lib.brmi_shadow_capture.argtypes = [vp, f32, f32, C.POINTER(TextureDesc), vp]
             lib.brmi_debug_shadow.argtypes = [vp, u32, vp, vp, vp, u32, vp]
+        if hasattr(lib, "brmi_set_temporal"):
+            lib.brmi_temporal_default_settings.argtypes = [C.POINTER(TemporalSettings)]
+            lib.brmi_temporal_default_settings.restype = None
+            lib.brmi_temporal_get_layout.argtypes = [u32, u32, C.POINTER(TemporalLayout)]
+            lib.brmi_set_temporal.argtypes = [vp, C.POINTER(TemporalBuffers)]
+            lib.brmi_temporal_resolve.argtypes = [vp, vp]
+            lib.brmi_temporal_reset.argtypes = [vp]
+            lib.brmi_temporal_state.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+            lib.brmi_debug_temporal_resolve.argtypes = [u32, u32, vp, vp, vp, vp, vp, C.POINTER(TemporalSettings), vp]
         _brmi_lib = lib
     return _brmi_lib

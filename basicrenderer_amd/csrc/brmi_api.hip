@@ -322,6 +322,7 @@ int brmi_set_scene(brmi_pass* p, const brmi_scene_buffers* scene) {
     p->scene = *scene; p->haveScene = false; p->setupDone = false;
     p->streaming.on = false;      // (bound to the group table of the scene before: brmi_set_streaming again)
     p->samplerAniso = nullptr;    // (one word per sampler of the scene before: brmi_set_sampler_anisotropy again)
+    p->temporal.valid = false;    // (last frame's resolved image shows another scene: the next resolve writes the current frame)
     p->shadows.on = false; p->shadows.b = brmi_shadow_buffers{};      // (validated against the lights and cameras of the scene before: brmi_set_shadows again)
     const brmi_scene_buffers& sc = p->scene;
     if (!sc.slabs || !sc.perObject || !sc.perMesh || !sc.perMeshInstance || !sc.clodOffsets || !sc.meshMetadata || !sc.lodNodes || !sc.lodGroups ||
@@ -845,6 +846,83 @@ int brmi_display_resolve(brmi_pass* p, brmi_stream stream) {
     if (int rc = display_refusal(p, "brmi_display_resolve")) return rc;
     return brmi::launch_display_resolve(p, static_cast<hipStream_t>(stream));
 }
+// ---- temporal anti-aliasing (brmi_temporal.hip): every refusal comes before the first launch
+void brmi_temporal_default_settings(brmi_temporal_settings* s) {
+    if (!s) return;
+    *s = brmi_temporal_settings{};
+    s->structSize = (uint32_t)sizeof(brmi_temporal_settings); s->blend = 0.1f; s->phases = 16u;
+}
+int brmi_temporal_get_layout(uint32_t width, uint32_t height, brmi_temporal_layout* layout) {
+    if (!layout || width == 0u || height == 0u) return BRMI_ERR_INVALID;
+    *layout = brmi_temporal_layout{};
+    layout->historyBytes = brmi::temporal_image_bytes(width, height); layout->tilesX = (width + 7u) / 8u; layout->tilesY = (height + 7u) / 8u;
+    return BRMI_OK;
+}
+// why the settings cannot be used (null: they can)
+static const char* temporal_settings_refusal(const brmi_temporal_settings& st) {
+    if (st.structSize != sizeof(brmi_temporal_settings)) return "settings.structSize is not sizeof(brmi_temporal_settings)";
+    if (!std::isfinite(st.blend) || !(st.blend > 0.0f) || st.blend > 1.0f) return "blend must be finite and in (0, 1]";
+    if (st.phases == 0u) return "phases is 0";
+    for (uint32_t r : st.reserved) if (r) return "a reserved word is not zero";
+    return nullptr;
+}
+int brmi_set_temporal(brmi_pass* p, const brmi_temporal_buffers* b) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (!b) { p->temporal.on = false; p->temporal.b = brmi_temporal_buffers{}; p->temporal.valid = false; p->temporal.last = 1u; return BRMI_OK; }
+    if (b->structSize != sizeof(brmi_temporal_buffers)) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_temporal: structSize %u, expected %zu", b->structSize, sizeof(brmi_temporal_buffers));
+    if (const char* why = temporal_settings_refusal(b->settings)) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_temporal: %s", why);
+    if (b->reserved) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_temporal: a reserved word is not zero");
+    // a pixel's neighbourhood and its history taps reach rows another GPU owns: no partition of the frame
+    if (p->cfg.bandY0 != 0u || (p->cfg.bandY1 != 0u && p->cfg.bandY1 < p->cfg.height) || p->bandY0 != 0u || p->bandY1 < p->cfg.height || p->cfg.dynamicBand || p->stripes.count > 1u)
+        return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_temporal: not with a row band, dynamicBand or the interleaved partition (the neighbourhood and the history taps cross rows)");
+    if (p->history || !p->historyUsers.empty())
+        return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_temporal: the pass is linked to another by brmi_set_history_source (each pass would hold every second frame's history)");
+    const uint64_t need = brmi::temporal_image_bytes(p->cfg.width, p->cfg.height);
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(b->history[0]), a1 = reinterpret_cast<uintptr_t>(b->history[1]);
+    if (!a0 || !a1) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_temporal: a null image");
+    if ((a0 & 15u) || (a1 & 15u)) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_temporal: the images must be 16 B aligned");
+    if (b->historyBytes < need) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_temporal: an image holds %llu bytes, %u x %u pixels need %llu", (unsigned long long)b->historyBytes, p->cfg.width, p->cfg.height, (unsigned long long)need);
+    if (a0 < a1 + need && a1 < a0 + need) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_temporal: the two images overlap");
+    p->temporal.b = *b; p->temporal.on = true; p->temporal.valid = false; p->temporal.last = 1u;      // (the first resolve writes image 0)
+    return BRMI_OK;
+}
+// what keeps the temporal stage from running (host state only: brmi_execute_split asks before the frame's first launch)
+static int temporal_refusal(brmi_pass* p, const char* what) {
+    if (!p->setupDone || !p->updated) return brmi::fail(p, BRMI_ERR_STATE, "%s: setup/update not done", what);
+    if (!p->temporal.on) return brmi::fail(p, BRMI_ERR_STATE, "%s: no history images bound (brmi_set_temporal)", what);
+    if (p->bandY0 != 0u || p->bandY1 < p->cfg.height) return brmi::fail(p, BRMI_ERR_STATE, "%s: the pass renders a row band", what);
+    if (!p->res[BRMI_RES_HDR_COLOR] || !p->res[BRMI_RES_LINEAR_DEPTH] || !p->res[BRMI_RES_GBUF_MOTION_VECTORS]) return brmi::fail(p, BRMI_ERR_STATE, "%s: the HDR, depth or motion-vector surface is not bound", what);
+    return BRMI_OK;
+}
+int brmi_temporal_resolve(brmi_pass* p, brmi_stream stream) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (int rc = temporal_refusal(p, "brmi_temporal_resolve")) return rc;
+    return brmi::launch_temporal_resolve(p, static_cast<hipStream_t>(stream));
+}
+int brmi_temporal_reset(brmi_pass* p) {
+    if (!p) return BRMI_ERR_INVALID;
+    if (!p->temporal.on) return brmi::fail(p, BRMI_ERR_STATE, "brmi_temporal_reset: no history images bound (brmi_set_temporal)");
+    p->temporal.valid = false;
+    return BRMI_OK;
+}
+int brmi_temporal_state(const brmi_pass* p, uint32_t* resolvedIndex, uint32_t* historyValid) {
+    if (!p || !p->temporal.on) return p ? BRMI_ERR_STATE : BRMI_ERR_INVALID;
+    if (resolvedIndex) *resolvedIndex = p->temporal.last;
+    if (historyValid) *historyValid = p->temporal.valid ? 1u : 0u;
+    return BRMI_OK;
+}
+int brmi_debug_temporal_resolve(uint32_t width, uint32_t height, const void* hdr, const void* depth, const void* motion, const void* history, void* out,
+                                const brmi_temporal_settings* settings, brmi_stream stream) {
+    if (width == 0u || height == 0u || width > 65536u || height > 65536u) return stage_fail(BRMI_ERR_INVALID, "brmi_debug_temporal_resolve: a frame of %u x %u pixels", width, height);
+    if (!hdr || !depth || !motion || !out || !settings) return stage_fail(BRMI_ERR_INVALID, "brmi_debug_temporal_resolve: a null surface or null settings");
+    if ((reinterpret_cast<uintptr_t>(hdr) & 7u) || (reinterpret_cast<uintptr_t>(history) & 7u) || (reinterpret_cast<uintptr_t>(out) & 7u) || !aligned4(depth) || !aligned4(motion))
+        return stage_fail(BRMI_ERR_INVALID, "brmi_debug_temporal_resolve: hdr, history and out must be 8 B aligned, depth and motion 4 B");
+    if (out == hdr || out == history) return stage_fail(BRMI_ERR_INVALID, "brmi_debug_temporal_resolve: out is one of the inputs");
+    if (const char* why = temporal_settings_refusal(*settings)) return stage_fail(BRMI_ERR_INVALID, "brmi_debug_temporal_resolve: %s", why);
+    g_stageError.clear();
+    const hipError_t e = brmi::launch_temporal_surfaces(width, height, hdr, depth, motion, history, out, settings->blend, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? BRMI_OK : stage_fail(BRMI_ERR_HIP, "launch k_temporal_resolve: %s", hipGetErrorString(e));
+}
 int brmi_streaming_feedback(brmi_pass* p, brmi_stream stream) {
     CHECK_READY(p);
     if (!p->streaming.on) return brmi::fail(p, BRMI_ERR_STATE, "brmi_streaming_feedback: no streaming buffers bound (brmi_set_streaming)");
@@ -899,6 +977,7 @@ int brmi_set_history_source(brmi_pass* p, brmi_pass* source) {
     if (!p) return BRMI_ERR_INVALID;
     if (source == p) source = nullptr;
     if (source) {
+        if (p->temporal.on || source->temporal.on) return brmi::fail(p, BRMI_ERR_INVALID, "brmi_set_history_source: not with a temporal binding (brmi_set_temporal) on either pass");
         if (!p->setupDone || !source->setupDone) return brmi::fail(p, BRMI_ERR_STATE, "brmi_set_history_source: both passes need brmi_setup first");
         if (!p->cfg.enableOcclusionCulling || !source->cfg.enableOcclusionCulling) return brmi::fail(p, BRMI_ERR_STATE, "brmi_set_history_source: both passes need enableOcclusionCulling (there is no history otherwise)");
         if (p->cfg.width != source->cfg.width || p->cfg.height != source->cfg.height || ((p->bandY0 != source->bandY0 || p->bandY1 != source->bandY1) && !(p->cfg.dynamicBand && source->cfg.dynamicBand)))
@@ -934,6 +1013,7 @@ int brmi_execute_split(brmi_pass* p, brmi_stream stream, brmi_stream shadeStream
     const bool skybox = p->env.on && p->env.b.skybox;      // ... and so is a skybox stage that could not run
     if (skybox && (rc = skybox_refusal(p))) return rc;
     if (p->gtao.on && (rc = gtao_refusal(p, "brmi_execute"))) return rc;      // ... and the GTAO stages of a bound term
+    if (p->temporal.on && (rc = temporal_refusal(p, "brmi_execute"))) return rc;      // ... and the temporal resolve of bound history images
     if (p->display.on && (rc = display_refusal(p, "brmi_execute"))) return rc;      // ... and the display chain of a bound target
     p->executesSinceTimes++;
     const bool split = shadeStream != stream;
@@ -996,6 +1076,8 @@ int brmi_execute_split(brmi_pass* p, brmi_stream stream, brmi_stream shadeStream
     if ((rc = stage_shade(p, ctx, stream, p->gtao.on))) return rc;
     // SkyboxRenderPass behind the deferred shading (the reference's Deferred -> Skybox -> Forward), only where the bound environment asks for it
     if (skybox && (rc = brmi_skybox(p, stream))) return rc;
+    // the temporal resolve where the reference runs its upscaler: behind the skybox, ahead of the display chain, which then reads the resolved image
+    if (p->temporal.on && (rc = brmi::launch_temporal_resolve(p, static_cast<hipStream_t>(stream)))) return rc;
     // LuminanceHistogram(+Average)Pass, BuildBloomPipeline and TonemappingPass behind the lit frame, on the shading stream, in front of the frame's end
     if (p->display.on) {
         hipStream_t ds = static_cast<hipStream_t>(stream);

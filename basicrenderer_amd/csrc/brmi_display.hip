@@ -180,8 +180,8 @@ void display_layout(uint32_t width, uint32_t height, brmi_display_layout* l) {
     l->ldrBytes = (uint64_t)width * height * 4u;
     l->blendedHdrBytes = (uint64_t)((width + 7u) / 8u) * ((height + 7u) / 8u) * 64u * 8u;
 }
-static Level level_of(const brmi_pass* p, uint32_t level) {      // 0: the pass's HDR target
-    if (level == 0u) return Level{static_cast<uint2*>(p->res[BRMI_RES_HDR_COLOR]), p->cfg.width, p->cfg.height, p->tilesX};
+static Level level_of(const brmi_pass* p, uint32_t level) {      // 0: the pass's HDR target (the resolved image of a bound temporal stage); only read
+    if (level == 0u) return Level{static_cast<uint2*>(const_cast<void*>(display_input_of(p))), p->cfg.width, p->cfg.height, p->tilesX};
     const brmi_display_plane& pl = p->display.layout.bloom[level - 1u];
     return Level{reinterpret_cast<uint2*>(static_cast<uint8_t*>(p->display.b.scratch) + pl.offset), pl.width, pl.height, (pl.width + 7u) / 8u};
 }
@@ -197,7 +197,7 @@ int launch_display_exposure(brmi_pass* p, hipStream_t s, bool histogramOnly) {
         return BRMI_OK;
     }
     HistogramArgs h{};
-    h.hdr = static_cast<const uint2*>(p->res[BRMI_RES_HDR_COLOR]); h.histogram = scratch_at<uint32_t>(p, l.histogramOffset);
+    h.hdr = static_cast<const uint2*>(display_input_of(p)); h.histogram = scratch_at<uint32_t>(p, l.histogramOffset);
     h.W = p->cfg.width; h.H = p->cfg.height; h.tilesX = p->tilesX; h.tileCount = p->tilesX * p->tilesY;
     h.minLog = st.minLogLuminance; h.invRange = 1.0f / st.logLuminanceRange;
     const uint32_t groups = std::min((h.tileCount + 3u) / 4u, 1024u);      // every wave walks tiles: at 4K a workgroup adds its bins once for 126 tiles
@@ -245,7 +245,7 @@ template <bool BLOOM> static void launch_resolve_of(uint32_t curve, dim3 grid, h
 int launch_display_resolve(brmi_pass* p, hipStream_t s) {
     const brmi_display_settings& st = p->display.b.settings;
     ResolveArgs a{};
-    a.hdr = static_cast<const uint2*>(p->res[BRMI_RES_HDR_COLOR]);
+    a.hdr = static_cast<const uint2*>(display_input_of(p));
     a.control = scratch_at<uint32_t>(p, p->display.layout.controlBlockOffset);
     a.ldr = static_cast<uint32_t*>(p->display.b.ldr);
     a.W = p->cfg.width; a.H = p->cfg.height; a.tilesX = p->tilesX;

@@ -432,6 +432,8 @@ struct brmi_pass {
     struct { bool on = false; brmi_environment_buffers b{}; } env;      // brmi_set_environment (kept by brmi_set_scene: nothing of it depends on the scene)
     struct { bool on = false; brmi_gtao_buffers b{}; brmi_gtao_layout layout{}; } gtao;      // brmi_set_gtao (kept by brmi_set_scene: sized by the frame alone)
     struct { bool on = false; brmi_display_buffers b{}; brmi_display_layout layout{}; } display;      // brmi_set_display (kept by brmi_set_scene: sized by the frame alone)
+    // brmi_set_temporal (kept by brmi_set_scene, which invalidates the history): `last` is the image the last resolve wrote, `valid` whether the next one reads it
+    struct { bool on = false; brmi_temporal_buffers b{}; uint32_t last = 1u; bool valid = false; } temporal;
     // brmi_set_shadows (forgotten by brmi_set_scene: validated against the scene's lights and cameras)
     struct { bool on = false; brmi_shadow_buffers b{}; } shadows;
     uint32_t frameIndexHost = 0;                 // brmi_frame_update::frameIndex of the last brmi_update (the GTAO noise's temporal index)
@@ -500,6 +502,12 @@ int launch_display_exposure(brmi_pass* p, hipStream_t s, bool histogramOnly = fa
 int launch_display_bloom(brmi_pass* p, hipStream_t s);
 int launch_display_bloom_pass(brmi_pass* p, uint32_t mipIndex, bool isUpsample, hipStream_t s);
 int launch_display_resolve(brmi_pass* p, hipStream_t s);
+// brmi_temporal.hip (the entry points have checked the binding / the surfaces)
+uint64_t temporal_image_bytes(uint32_t width, uint32_t height);
+hipError_t launch_temporal_surfaces(uint32_t width, uint32_t height, const void* hdr, const void* depth, const void* motion, const void* history, void* out, float blend, hipStream_t s);
+int launch_temporal_resolve(brmi_pass* p, hipStream_t s);
+// what the display chain reads: the resolved image of a bound temporal stage, the HDR target otherwise
+inline const void* display_input_of(const brmi_pass* p) { return p->temporal.on ? p->temporal.b.history[p->temporal.last] : p->res[BRMI_RES_HDR_COLOR]; }
 int launch_env_convert(const brmi_texture_desc* equirect, const brmi_texture_desc* cube, uint32_t size, hipStream_t s);
 int launch_env_project_sh(const brmi_texture_desc* cubemaps, uint32_t cubemapCount, brmi_environment_info* env, uint32_t size, hipStream_t s);
 int launch_env_prefilter(const brmi_texture_desc* source, const brmi_texture_desc* prefiltered, uint32_t size, uint32_t levels, hipStream_t s);

@@ -16,7 +16,9 @@
 // (BR/src/Renderer.cpp:2112-2122).
 #pragma once
 
+#include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <functional>
 #include <memory>
 #include <stdexcept>
@@ -150,6 +152,12 @@ BRMI_STAGE_PASS(DeferredShadingPass, "DeferredShadingPass", brmi_shade(state->ge
                   "Builtin::GBuffer::MetallicRoughness", "Builtin::PrimaryCamera::LinearDepthMap", "Builtin::Light::ClusterBuffer", "Builtin::Light::PagesBuffer",
                   "Builtin::OpenPBR::*"}),
                 ({"Builtin::Color::HDRColorTarget"}))
+// reference: UpscalingPass between the lit frame and the display chain (BR/src/Renderer.cpp:2640-2666), whose resolvers are DLSS / FSR binaries; here the
+// native-resolution temporal resolve.  The history images are the graph's (brmi_set_temporal on PassState's handle, brmi_temporal_get_layout for
+// their size); off until they are bound.  With it bound the three display stages below read UpscaledHDR, as the reference's do.
+BRMI_STAGE_PASS(UpscalingPass, "UpscalingPass", brmi_temporal_resolve(state->get(), ctx.commandList),
+                ({"Builtin::Color::HDRColorTarget", "Builtin::PrimaryCamera::LinearDepthMap", "Builtin::GBuffer::MotionVectors", "Builtin::PostProcessing::UpscaledHDR(history)"}),
+                ({"Builtin::PostProcessing::UpscaledHDR"}))
 // reference: the display chain behind the lit frame (BR/src/Renderer.cpp:2667-2704, RenderGraphBuildHelper.h:504-530).  Five reference passes, three stages:
 //   LuminanceHistogramPass + LuminanceHistogramAveragePass                                   -> brmi_display_exposure
 //   BloomDownsamplePass0..4 + BloomUpsamplePass4..1                                          -> brmi_display_bloom
@@ -163,6 +171,45 @@ BRMI_STAGE_PASS(TonemappingPass, "TonemappingPass", brmi_display_resolve(state->
                 ({"Builtin::Color::HDRColorTarget", "Builtin::PostProcessing::UpscaledHDR(mip 1)", "FFX::LPMConstants"}), ({"back buffer (R8G8B8A8_UNorm)", "Builtin::PostProcessing::UpscaledHDR"}))
 #undef BRMI_STAGE_PASS
 #undef BRMI_STAGE_PASS_WITH
+
+// ---- the jittered camera (BR/src/Renderer.cpp:908-924, UpscalingManager::GetJitter's DLSS branch, MathUtils.cpp Halton), as basicrenderer_amd/temporal.py has it ----
+inline float Halton(uint32_t i, uint32_t b) {
+    float f = 1.0f, r = 0.0f;
+    while (i > 0u) { f /= (float)b; r = r + f * (float)(i % b); i = (uint32_t)std::floor((float)i / (float)b); }
+    return r;
+}
+// (jx, jy) in pixels, each in [-0.5, 0.5): the frame's offset in a sequence of `phases` (brmi_temporal_settings::phases)
+inline void jitter_offset(uint32_t frameIndex, uint32_t phases, float& jx, float& jy) {
+    const uint32_t i = frameIndex % (phases ? phases : 1u);
+    jx = Halton(i + 1u, 2u) - 0.5f; jy = Halton(i + 1u, 3u) - 0.5f;
+}
+// projection = unjitteredProjection x Translation(2 jx / W, -2 jy / H, 0); viewProjection, projectionInverse and the culling camera follow from it in double,
+// rounded once; unjitteredProjection stays; with `previous` (last frame's record) the two prev* projections take its projection and unjitteredProjection.
+inline void jitter_camera(brmi_camera& c, brmi_culling_camera& cc, uint32_t width, uint32_t height, float jx, float jy, const brmi_camera* previous = nullptr) {
+    const float tx = 2.0f * jx / (float)width, ty = -2.0f * jy / (float)height;
+    double p[4][4], inv[4][8];
+    for (int r = 0; r < 4; r++) for (int k = 0; k < 4; k++) p[r][k] = (double)c.unjitteredProjection[r][k];
+    for (int r = 0; r < 4; r++) { p[r][0] += p[r][3] * (double)tx; p[r][1] += p[r][3] * (double)ty; }
+    for (int r = 0; r < 4; r++) for (int k = 0; k < 4; k++) { c.projection[r][k] = (float)p[r][k]; p[r][k] = (double)c.projection[r][k]; }
+    for (int r = 0; r < 4; r++) for (int k = 0; k < 4; k++) {
+        double s = 0.0;
+        for (int j = 0; j < 4; j++) s += (double)c.view[r][j] * p[j][k];
+        c.viewProjection[r][k] = (float)s;
+    }
+    for (int r = 0; r < 4; r++) for (int k = 0; k < 8; k++) inv[r][k] = k < 4 ? p[r][k] : (k - 4 == r ? 1.0 : 0.0);      // Gauss-Jordan with partial pivoting
+    for (int col = 0; col < 4; col++) {
+        int pivot = col;
+        for (int r = col + 1; r < 4; r++) if (std::fabs(inv[r][col]) > std::fabs(inv[pivot][col])) pivot = r;
+        for (int k = 0; k < 8; k++) { const double t = inv[col][k]; inv[col][k] = inv[pivot][k]; inv[pivot][k] = t; }
+        const double d = inv[col][col];
+        for (int k = 0; k < 8; k++) inv[col][k] /= d;
+        for (int r = 0; r < 4; r++) if (r != col) { const double f = inv[r][col]; for (int k = 0; k < 8; k++) inv[r][k] -= f * inv[col][k]; }
+    }
+    for (int r = 0; r < 4; r++) for (int k = 0; k < 4; k++) c.projectionInverse[r][k] = (float)inv[r][k + 4];
+    if (previous) { std::memcpy(c.prevJitteredProjection, previous->projection, 64); std::memcpy(c.prevUnjitteredProjection, previous->unjitteredProjection, 64); }
+    cc.projX = c.projection[0][0]; cc.projY = c.projection[1][1];
+    std::memcpy(cc.viewProjection, c.viewProjection, 64); std::memcpy(cc.projectionInverse, c.projectionInverse, 64);
+}
 
 // ---- the extension interface (BR/include/Render/GraphExtensions/CLodExtension.h:20-31) ------------------------------------------
 // Stand-ins for the graph-side types the five hooks take (OpenRenderGraph is an empty submodule in the reference checkout).

@@ -81,6 +81,7 @@ class VisibilityRenderer:
         self._environment, self._environment_index = None, 0      # set_environment's device tables, perFrame.activeEnvironmentIndex of this pass's frames
         self._debug_mode, self._debug_view, self._pf_own = 0, None, None      # set_debug_view: outputType, the targets, this pass's per-frame record
         self._frame_index = 0        # of the last brmi_update
+        self._temporal = None        # set_temporal's history images and jitter state
         self.descs = {}
 
         def cb(_user, d):
@@ -160,6 +161,8 @@ class VisibilityRenderer:
     def set_camera_device(self, cameras_dev, culling_cameras_dev, cameras_host, frame_index=0):
         """Next frame's camera from buffers already in HBM (uint8 tensors with the bytes of Scene.camera_at): two device-to-device copies on the
         current stream into this pass's camera buffers, then brmi_update with the host copy of the same camera."""
+        if self._temporal is not None:
+            raise BrmiError("set_camera_device: not with a temporal binding (the jitter is applied to host camera bytes: set_camera_from)")
         self.device_arrays["cameras"].copy_(cameras_dev, non_blocking=True)
         self.device_arrays["cullingCameras"].copy_(culling_cameras_dev, non_blocking=True)
         upd = capi.FrameUpdate(cameras_host.ctypes.data, self._per_frame_host(self.scene).ctypes.data, frame_index)
@@ -183,6 +186,21 @@ class VisibilityRenderer:
         self._pf_own.view(np.uint32)[capi.PER_FRAME_ACTIVE_ENVIRONMENT_WORD] = self._environment_index
         return self._pf_own
 
+    def _upload_cameras(self, cam, cull):
+        for name, a in (("cameras", cam), ("cullingCameras", cull)):
+            self.device_arrays[name][: len(a)].copy_(self.torch.from_numpy(np.ascontiguousarray(a)).to(self.device))
+
+    def _jittered_camera(self, src, frame_index):
+        """set_temporal: the camera of `src` jittered by frame_index, uploaded to this pass's camera buffers; the host copy of it."""
+        from . import temporal as tmod
+        t = self._temporal
+        if t["current"] is not None and t["current_index"] != frame_index:      # (an update() repeated for one frame keeps that frame's predecessor)
+            t["previous"] = t["current"]
+        cam, cull = tmod.jitter_camera(src.arrays["cameras"], src.arrays["cullingCameras"], self.W, self.H, tmod.jitter_offset(frame_index, t["phases"]), previous=t["previous"])
+        t["current"], t["current_index"] = cam, frame_index
+        self._upload_cameras(cam, cull)
+        return cam
+
     def update(self, frame_index=0):
         self._frame_index = frame_index
         if getattr(self, "_cam_bytes", None) is not None:
@@ -191,6 +209,8 @@ class VisibilityRenderer:
             return
         src = getattr(self, "_cam_scene", self.scene)
         cam, pf = src.camera_host(), self._per_frame_host(src)
+        if self._temporal is not None:
+            cam = self._jittered_camera(src, frame_index)
         upd = capi.FrameUpdate(cam.ctypes.data, pf.ctypes.data, frame_index)
         self._check(self.lib.brmi_update(self._h, C.byref(upd), self._s()), "brmi_update")
 
@@ -599,6 +619,65 @@ class VisibilityRenderer:
         d["scratch"][int(lay.histogramOffset): int(lay.histogramOffset) + 1024].zero_()
         d["scratch"][int(lay.adaptedLuminanceOffset): int(lay.adaptedLuminanceOffset) + 4].zero_()
 
+    # -- temporal anti-aliasing (brmi_set_temporal) -------------------------------------------------
+    def temporal_layout(self):
+        lay = capi.TemporalLayout()
+        self._check(self.lib.brmi_temporal_get_layout(capi.u32(self.W), capi.u32(self.H), C.byref(lay)), "brmi_temporal_get_layout", use_pass=False)
+        return lay
+
+    def set_temporal(self, blend=0.1, phases=16, fill=0, guard=0):
+        """Temporal anti-aliasing from the next frame on: update(frame_index) jitters this pass's camera by temporal.jitter_offset(frame_index, phases), execute()
+        resolves the lit frame against last frame's resolved image behind the skybox, and the display chain reads resolved_hdr().  blend: the current frame's
+        weight; None for off -- the camera bytes and the frames of a pass that never called this.  The two history images are this pass's own tensors (every
+        byte `fill` to start with, `guard` more bytes behind each that the library is not told about: temporal_guard_intact()).  Binding again restarts the
+        accumulation.  Repeats the last update()."""
+        torch = self.torch
+        if self._temporal is not None:
+            torch.cuda.synchronize(self.device)
+        if blend is None:
+            self._check(self.lib.brmi_set_temporal(self._h, None), "brmi_set_temporal")
+            had, self._temporal = self._temporal is not None, None
+            if had and getattr(self, "_cam_bytes", None) is None:      # the camera as it was before the jitter
+                src = getattr(self, "_cam_scene", self.scene)
+                self._upload_cameras(src.arrays["cameras"], src.arrays["cullingCameras"])
+                self.update(self._frame_index)
+            return
+        if getattr(self, "_cam_bytes", None) is not None:
+            raise BrmiError("set_temporal: the pass's camera came from set_camera_device (the jitter is applied to host camera bytes: set_camera_from)")
+        lay = self.temporal_layout()
+        images = [torch.full((int(lay.historyBytes) + int(guard),), int(fill), dtype=torch.uint8, device=self.device) for _ in range(2)]
+        b = capi.TemporalBuffers()
+        b.structSize = C.sizeof(capi.TemporalBuffers)
+        self.lib.brmi_temporal_default_settings(C.byref(b.settings))
+        b.settings.blend, b.settings.phases = float(blend), int(phases)
+        b.history[0], b.history[1], b.historyBytes = images[0].data_ptr(), images[1].data_ptr(), int(lay.historyBytes)
+        self._check(self.lib.brmi_set_temporal(self._h, C.byref(b)), "brmi_set_temporal")
+        self._temporal = dict(buffers=b, images=images, layout=lay, fill=int(fill), phases=int(phases), previous=None, current=None, current_index=None)
+        self.update(self._frame_index)
+
+    def _temporal_bound(self, what):
+        if self._temporal is None:
+            raise BrmiError(f"{what}: set_temporal first")
+        self.torch.cuda.synchronize(self.device)
+        return self._temporal
+
+    def resolved_hdr(self):
+        """(H, W) uint64: the last frame as the temporal resolve left it (four halves a pixel), detiled like hdr()."""
+        t = self._temporal_bound("resolved_hdr")
+        index = capi.u32(0)
+        self._check(self.lib.brmi_temporal_state(self._h, C.byref(index), None), "brmi_temporal_state")
+        return detile(t["images"][index.value][: int(t["layout"].historyBytes)].cpu().numpy().view(np.uint64), self.W, self.H)
+
+    def temporal_reset(self):
+        """The next frame's resolve has no history: it writes the current frame, as the first one did."""
+        self._temporal_bound("temporal_reset")
+        self._check(self.lib.brmi_temporal_reset(self._h), "brmi_temporal_reset")
+
+    def temporal_guard_intact(self):
+        """True while the guard bytes behind set_temporal's two history images still hold their fill."""
+        t = self._temporal_bound("temporal_guard_intact")
+        return all(bool((img[int(t["layout"].historyBytes):] == t["fill"]).all()) for img in t["images"])
+
     # -- shadow maps of spot and point lights (brmi_set_shadows) ------------------------------------
     def set_shadows(self, lights, resolution=1024, point_resolution=512):
         """Shadows from the next frame on for `lights` (indices into the scene's light buffer; spot and point lights only), or None for off -- exactly the
@@ -805,6 +884,7 @@ class VisibilityRenderer:
             self._environment = None
             self._gtao = None
             self._display = None
+            self._temporal = None
             if getattr(self, "_shadows", None) is not None:
                 for r in self._shadows["passes"].values():
                     r.close()

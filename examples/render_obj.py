@@ -3,7 +3,7 @@
 (Reinhard + sRGB), or -- with --tonemap -- the RGBA8 picture of the library's display chain (auto-exposure, bloom, tone mapping).
 
     python examples/render_obj.py model.obj|scene.glb out.png [--size 1920x1080] [--lights 32] [--features 0] [--environment sky] [--gtao] [--shadows] [--view NAME]
-                                  [--tonemap reinhard|neutral|aces|lpm|none] [--bloom] [--exposure-frames 8]
+                                  [--tonemap reinhard|neutral|aces|lpm|none] [--bloom] [--exposure-frames 8] [--taa N]
 
 --view NAME writes a debug view of the frame instead (perFrame.outputType: normal, albedo, metallic, roughness, emissive, ao, depth, meshlets,
 geometry_group, light_cluster_id, light_cluster_light_count, motion_vectors); pixels without geometry are black.
@@ -43,6 +43,7 @@ def main():
     ap.add_argument("--tonemap", default=None, choices=["reinhard", "neutral", "aces", "lpm", "none"], help="write the RGBA8 of the library's display chain with this curve (default: off, the file as before)")
     ap.add_argument("--bloom", action="store_true", help="with --tonemap: the bloom pyramid blended into the frame (both sides of the frame at least 32 pixels)")
     ap.add_argument("--exposure-frames", type=int, default=8, metavar="N", help="with --tonemap: render N frames, the last N - 2 with time coefficient 1, so the auto-exposure has settled")
+    ap.add_argument("--taa", type=int, default=0, metavar="N", help="temporal anti-aliasing: render N jittered frames of the still camera and write the last resolved one (with --tonemap: through the display chain)")
     ap.add_argument("--shadows", action="store_true", help="shadow maps for every spot and point light of the scene (rendered once, from each light's own views)")
     ap.add_argument("--shadow-size", type=int, default=1024, metavar="N", help="with --shadows: a spot map is N x N, a cube face N/2 x N/2")
     ap.add_argument("--procedural-materials", action="store_true", help="a glTF file's own materials and textures are used by default; this keeps the procedural stand-ins (--features)")
@@ -84,20 +85,32 @@ def main():
         ap.error("--bloom needs --tonemap")
     if a.tonemap and a.view:
         ap.error("--tonemap and --view write different pictures: give one of them")
+    if a.taa and a.view:
+        ap.error("--taa and --view write different pictures: give one of them")
+    if a.taa:
+        r.set_temporal()
+
+    def frame(k):      # with --taa: frame k's jitter; without a skybox the shading pass leaves pixels without geometry alone, so the target is cleared here
+        if a.taa:
+            if not a.skybox:
+                r.hdr_tensor().zero_()
+            r.update(k)
+        r.execute()
     if a.tonemap:
-        frames = max(a.exposure_frames, 1)
+        frames = max(a.exposure_frames, a.taa, 1)
         for k in range(frames):      # the first two frames bring the path's own history up; from then on the adaptation jumps to the frame's average
             r.set_display(a.tonemap, bloom=a.bloom, time_coefficient=1.0 if k >= min(2, frames - 1) else 0.0)
-            r.execute()
+            frame(k)
         write_png(a.png, np.ascontiguousarray(r.ldr()[..., :3]))
         print(f"{a.obj}: {a.tonemap}{' + bloom' if a.bloom else ''}, adapted luminance {r.adapted_luminance():.4g} after {frames} frames -> {a.png}")
         return
-    r.execute(); r.execute()
+    for k in range(max(a.taa, 2)):
+        frame(k)
     if a.view:
         write_png(a.png, np.ascontiguousarray(r.debug_image()[..., :3]))
         print(f"{a.obj}: debug view {a.view} -> {a.png}")
         return
-    hdr = r.hdr().view(np.float16).reshape(h, w, 4)[..., :3].astype(np.float32)
+    hdr = (r.resolved_hdr() if a.taa else r.hdr()).view(np.float16).reshape(h, w, 4)[..., :3].astype(np.float32)
     ldr = hdr / (1.0 + hdr)
     srgb = np.where(ldr <= 0.0031308, 12.92 * ldr, 1.055 * np.power(np.maximum(ldr, 1e-8), 1 / 2.4) - 0.055)
     write_png(a.png, (np.clip(srgb, 0, 1) * 255 + 0.5).astype(np.uint8))

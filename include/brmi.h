@@ -483,6 +483,52 @@ int  brmi_display_resolve(brmi_pass* pass, brmi_stream stream);
 int  brmi_debug_display_histogram(brmi_pass* pass, brmi_stream stream);      /* LuminanceHistogramPass alone: adds the frame's counts to the histogram */
 int  brmi_debug_display_bloom_pass(brmi_pass* pass, uint32_t mipIndex, uint32_t isUpsample, brmi_stream stream);
 
+/* ---- Temporal anti-aliasing: the stage between the lit frame and the display chain, where the reference runs its upscaler ------------------------
+ * The caller jitters the main camera's `projection` (brmi_passes.hpp: jitter_offset / jitter_camera; `unjitteredProjection` stays, so the motion plane does not see
+ * the jitter); the stage resolves the one-sample frame against last frame's resolved image at native resolution: a 3 x 3 neighbourhood box in w = c / (1 + max c),
+ * the motion vector of the closest of the nine pixels, a bilinear history sample, the clamp into the box, r = h + blend * (w(current) - h), the inverse of w.  Where
+ * there is no history (none yet, the reprojected position outside the frame, a sample that is not finite) the current colour passes unchanged.  Alpha is carried.
+ * Off by default: a pass that never calls brmi_set_temporal, or calls it with NULL, launches exactly what it launched before and writes the same bytes.  With it
+ * bound, brmi_execute / brmi_execute_split run brmi_temporal_resolve behind the skybox stage and ahead of the display chain, on the shading stream, and the display
+ * stages read the resolved image where they read the HDR target, which this stage never writes.
+ *
+ * `history[0]`, `history[1]`: two caller-owned images in the surfaces' tiled layout (brmi_temporal_get_layout: 8 B per pixel, whole tiles), 16 B aligned and not
+ * overlapping.  The pass reads the one it wrote last and writes the other.  After brmi_set_temporal, brmi_set_scene or brmi_temporal_reset the history is invalid:
+ * the next resolve writes the current frame.  Calling brmi_set_temporal again therefore also restarts the accumulation.
+ * A binding belongs to ONE pass.  One camera sequence rendered through several passes in flight (brmi_set_history_source) is not supported with a temporal binding:
+ * each pass would hold every second frame's history.  brmi_set_temporal refuses a pass that has a history source or is one, and brmi_set_history_source refuses a
+ * pass with a temporal binding.
+ * Refusals (BRMI_ERR_INVALID, before anything is launched): a wrong structSize (buffers or settings), a null, misaligned or short image, the two images overlapping,
+ * blend outside (0, 1] or not finite, phases 0, non-zero reserved words, a pass with a row band, dynamicBand or stripes (the taps cross rows), a history source. */
+typedef struct brmi_temporal_settings {
+    uint32_t structSize;        /* sizeof(brmi_temporal_settings) */
+    float    blend;             /* weight of the current frame, (0, 1]; default 0.1 */
+    uint32_t phases;            /* length of the jitter sequence the caller walks (jitter_offset); default 16.  The kernel does not read it. */
+    uint32_t reserved[5];       /* zero */
+} brmi_temporal_settings;       /* 32 B */
+typedef struct brmi_temporal_layout {
+    uint64_t historyBytes;      /* one history image: whole tiles, 8 B per pixel */
+    uint32_t tilesX, tilesY;
+} brmi_temporal_layout;         /* 16 B */
+typedef struct brmi_temporal_buffers {
+    uint32_t structSize;        /* sizeof(brmi_temporal_buffers) */
+    uint32_t reserved;
+    brmi_temporal_settings settings;
+    void*    history[2];
+    uint64_t historyBytes;      /* what EACH image holds */
+} brmi_temporal_buffers;        /* 64 B */
+void brmi_temporal_default_settings(brmi_temporal_settings* settings);
+int  brmi_temporal_get_layout(uint32_t width, uint32_t height, brmi_temporal_layout* layout);      /* BRMI_ERR_INVALID: a null layout or an empty frame */
+int  brmi_set_temporal(brmi_pass* pass, const brmi_temporal_buffers* buffers_or_NULL);
+int  brmi_temporal_resolve(brmi_pass* pass, brmi_stream stream);      /* the stage alone.  BRMI_ERR_STATE before brmi_setup / brmi_update, or when nothing is bound */
+int  brmi_temporal_reset(brmi_pass* pass);                            /* the next resolve has no history */
+/* Which of the two images holds the last resolved frame (0 or 1), and whether the next resolve has a history. */
+int  brmi_temporal_state(const brmi_pass* pass, uint32_t* resolvedIndex, uint32_t* historyValid);
+/* The kernel on caller-given device surfaces in the tiled layout (whole tiles each): hdr and out 8 B, depth and motion 4 B per pixel; history NULL = absent.
+ * Needs no pass; a refusal is read with brmi_last_error(NULL). */
+int  brmi_debug_temporal_resolve(uint32_t width, uint32_t height, const void* hdr, const void* depth, const void* motion, const void* history_or_NULL, void* out,
+                                 const brmi_temporal_settings* settings, brmi_stream stream);
+
 /* Debug views.  brmi_set_debug_view binds the targets (NULL unbinds and gives exactly the frames of a pass that never called it); with a target bound and
  * perFrame.outputType != 0, brmi_execute / brmi_execute_split run brmi_debug_view behind the shading stage (on the shading stream); an outputType the stage
  * would refuse makes them fail BEFORE anything is launched.  The lit HDR frame and
